@@ -27,10 +27,16 @@ At N > 1 every replica steps with eta0 and alpha times N^p (``--dp-lr-power``, d
 Timing: W untimed warmup steps, then barrier + synchronize, K timed steps, synchronize +
 barrier; the max over ranks is reported.  With fp32 state the first warmup step runs the
 learner's early-training ramp (``--ramp-rows``, the atomic-update kernel that ``train_ffm`` uses
-for its first 2^18 rows, docs/compat.md); the timed steps always run the default kernel.  After timing, rank 0 evaluates logloss of the mixed
-model on held-out rows and the planted model's logloss (the Bayes floor).
+for its first 2^18 rows, docs/compat.md); the timed steps always run the default kernel.
 
-On the GPU the same schedule then runs a second time with the other state precision in the
+A plain run stops there: it sets up, warms up, times the K steps, writes its outputs if asked
+and prints the result line.  ``--dump-state DIR``: a seeded sample of the model state the last
+timed step left (``dump_state``; on the GPU it carries the run-to-run noise of the lock-free
+updates).  ``--dump-outputs DIR``: what one more step through the timed path computes on rows
+that cannot race, the same arrays in every run (``dump_outputs``).  ``--full`` adds what the
+headline value does not need.  After timing, the mix cost is probed on its own (N > 1) and
+rank 0 evaluates logloss of the mixed model on held-out rows next to the planted model's logloss (the Bayes floor) and the pinned sequential reference.  On the GPU
+the same schedule then runs a second time with the other state precision in the
 same process, on the same rows: ``value_bf16_state`` / ``logloss_heldout_bf16`` (``--alt-run 0``
 skips it).  ``wall_s`` breaks the process's wall time down (data generation,
 setup, warmup, timed region, evaluation, the other-precision run).  ``HM_METRICS=<path>`` appends one JSON
@@ -114,7 +120,20 @@ def parse_args(argv=None):
                     help="row order inside each resident batch (ops/ffm_sched.py, a host pass "
                          "before timing; experiment: conflict-aware scheduling, docs/perf_notes.md)")
     ap.add_argument("--mix-probe", type=int, default=3,
-                    help="synchronous mixes timed after the run (ms, wire bytes, bus GB/s)")
+                    help="--full: synchronous mixes timed after the run (ms, wire bytes, bus GB/s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything the headline value does not need: "
+                         "the final mix and the held-out logloss next to the planted floor and the "
+                         "pinned sequential reference, the mix probe (--mix-probe), and the same "
+                         "schedule with the other state precision (--alt-run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps rank 0 writes what one more step through the timed "
+                         "path computes on rows that cannot race as DIR/<name>.npy: the same arrays "
+                         "in every run (dump_outputs)")
+    ap.add_argument("--dump-state", metavar="DIR", default=None,
+                    help="rank 0 writes a seeded sample of the model state the last timed step left "
+                         "as DIR/<name>.npy; on the GPU it carries the run-to-run noise of the "
+                         "lock-free updates (dump_state)")
     return ap.parse_args(argv)
 
 
@@ -170,8 +189,96 @@ def check_world(args, ctx) -> None:
         sys.exit(2)
 
 
-def run_schedule(args, ctx, idx, fld, val, y, state: str, data, metrics=None) -> dict:
-    """One full FFM schedule (fresh model, warmup, timed region, final mix, held-out logloss).
+# --dump-outputs / --dump-state write at most 64 MB each: V and G at as many features as fit
+# DUMP_VG_BYTES (fp32); --dump-outputs: the linear tables at the features of DUMP_LINEAR_ROWS
+# probe rows; --dump-state: the linear tables whole up to DUMP_LINEAR_FEATURES features
+DUMP_VG_BYTES = 24 << 20
+DUMP_LINEAR_ROWS = 16384
+DUMP_LINEAR_FEATURES = 1 << 20
+
+
+def _save_arrays(out_dir: str, arrays: dict) -> dict:
+    """``arrays`` as ``out_dir/<name>.npy`` (float32; ``*_rows`` ids float64, exact) -> {name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        t = t.detach().double() if name.endswith("_rows") else t.detach().float()
+        a = np.ascontiguousarray(t.cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def dump_state(out_dir: str, st: dict) -> dict:
+    """--dump-state: the model state the last timed step left behind (``ffm_step`` returns
+    nothing, it updates the state in place): ``V`` and ``G`` at a fixed sample of the features
+    (seeded, sorted; their ids in ``feature_rows``, as many as fit DUMP_VG_BYTES), the linear
+    FTRL tables ``w``, ``wz``, ``wn`` (whole up to DUMP_LINEAR_FEATURES features, else at the same
+    sample) and ``bias``.  The rows, the initial weights and the kernel's rounding seeds are the
+    same in every run, and on the CPU so is this state.  On the GPU the timed steps train
+    concurrent rows on shared features without locks (Hogwild), so two runs of ONE build differ:
+    measured on MI355X at the default shape, 20 + 5 steps, mean |dV| 5e-4 at rms 0.29 (max 0.35),
+    mean |dw| 4e-3 at rms 0.11.  Compare two builds against that noise, not bit for bit; the
+    arrays that are the same in every run are --dump-outputs'."""
+    V, G = st["V"], st["G"]
+    NF = V.shape[0]
+    per_row = 4 * (V[0].numel() + G[0].numel())
+    n = max(1, min(NF, DUMP_VG_BYTES // per_row))
+    rows = torch.randperm(NF, generator=torch.Generator().manual_seed(4711))[:n].sort().values
+    r = rows.to(V.device)
+    lin = slice(None) if NF <= DUMP_LINEAR_FEATURES else r
+    return _save_arrays(out_dir, {"feature_rows": rows, "V": V[r], "G": G[r], "w": st["w"][lin],
+                                  "wz": st["wz"][lin], "wn": st["wn"][lin], "bias": st["bias"]})
+
+
+def dump_outputs(out_dir: str, args, opts: str, hyper, dev, F: int, fld, val, y, lin_mode) -> dict:
+    """--dump-outputs: what a caller of the timed path receives from a step, the same in every run.
+
+    The state the timed steps leave is not (--dump-state, ``dump_state``): its run-to-run noise
+    is far above rounding, so it cannot show that two builds compute the same.  What is written
+    here is one more ``ffm_step`` call after the timed steps, through the timed path's code
+    (the trainer options, hyperparameters, state precision and layout, kernel variant, ``--grid``
+    and linear mode of a timed step), on inputs that cannot race: a fresh model of the same
+    seed, and the benchmark's own first rows (fields, values, labels) with their feature ids
+    replaced by a seeded permutation, so that no two slots of the batch share a feature.  It is
+    not a timed step: the batch holds NF // F rows at most (26,886 of the timed step's 262,144
+    at the default shape, so the automatic grid is smaller), it gets a ``loss`` buffer, and no
+    two of its rows contend for a feature.  It compares the step's arithmetic between builds;
+    what a build does under contention shows in --dump-state and in the suite's parity tests.
+
+    Files (float32 ``.npy``; ids float64): ``feature_rows`` = the features of the first probe
+    rows (as many as fit DUMP_VG_BYTES), ``V`` and ``G`` at those features, the linear FTRL tables
+    ``w``, ``wz``, ``wn`` at the features of the first DUMP_LINEAR_ROWS probe rows (their ids in
+    ``linear_rows``), ``bias`` and every probe row's ``loss``.  Returns {name: shape}."""
+    from hivemall_amd.models.ffm import FFMTrainer
+    from hivemall_amd.ops.ffm import ffm_step
+
+    NF = 1 << args.hash_bits
+    n = max(1, min(args.batch, y.shape[0], NF // F))
+    perm = torch.randperm(NF, generator=torch.Generator().manual_seed(4711))[:n * F]
+    pidx = perm.to(torch.int32).reshape(n, F).contiguous().to(dev)
+    tr = FFMTrainer(opts, device=dev)
+    tr.init_state(NF, F)
+    st = tr.state
+    loss = torch.zeros(n, dtype=torch.float32, device=dev)
+    ffm_step(st, pidx, None if fld is None else fld[:n], None if val is None else val[:n],
+             y[:n], hyper, train=True, grid=args.grid, loss=loss, lin_mode=lin_mode)
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+    per_row = 4 * F * (st["V"][0].numel() + st["G"][0].numel())
+    r = pidx[:max(1, DUMP_VG_BYTES // per_row)].reshape(-1).long()
+    lr = pidx[:DUMP_LINEAR_ROWS].reshape(-1).long()
+    return _save_arrays(out_dir, {"feature_rows": r, "V": st["V"][r], "G": st["G"][r],
+                                  "linear_rows": lr, "w": st["w"][lr], "wz": st["wz"][lr],
+                                  "wn": st["wn"][lr], "bias": st["bias"], "loss": loss})
+
+
+def run_schedule(args, ctx, idx, fld, val, y, state: str, data, metrics=None, dump=False) -> dict:
+    """One FFM schedule: fresh model, warmup, timed region; ``--dump-state`` / ``--dump-outputs``
+    right after it (``dump``: the headline run); with ``--full`` the mix probe, the final mix and the held-out
+    logloss.
 
     ``state``: "bf16" or "fp32" V|G storage.  Returns the timing / quality record."""
     from hivemall_amd.models.ffm import FFMTrainer
@@ -289,7 +396,14 @@ def run_schedule(args, ctx, idx, fld, val, y, state: str, data, metrics=None) ->
     out = {"elapsed_s": elapsed, "ms_per_step": 1000.0 * elapsed / max(1, args.steps),
            "rows_per_s": float(B) * world * args.steps / elapsed, "mixes_timed": mixes_timed,
            "mixed_bytes": int(sum(t.numel() * t.element_size() for t in mix_tensors)),
-           "dp_lr_scale": sc, "ramp_steps": ramp_steps}
+           "dp_lr_scale": sc, "ramp_steps": ramp_steps, "probe": {}, "mix_wire": wire, "ll": None}
+    if dump and rank == 0:
+        # the state first: the probe step trains a model of its own and leaves this one alone
+        if args.dump_state:
+            out["dumped_state"] = dump_state(args.dump_state, st)
+        if args.dump_outputs:
+            out["dumped"] = dump_outputs(args.dump_outputs, args, opts, hyper, dev, F, fld, val, y,
+                                         ffm_model.dp_lin_mode(world))
     if os.environ.get("HM_TRACE"):
         # host + device timeline of a few extra steps (outside the timed region)
         from hivemall_amd.prof import host_trace
@@ -301,14 +415,17 @@ def run_schedule(args, ctx, idx, fld, val, y, state: str, data, metrics=None) ->
                 overlap.finish()
             sync()
 
+    if not args.full:
+        out["wall"] = wall
+        mixer.release()
+        del tr, st
+        return out
     # ---- mix cost on its own (synchronous, outside the timed region); leaves the model mixed ----
     out["probe"] = mixer.probe(mix_tensors, args.mix_probe, fn=sync_mix) if world > 1 else {}
-    out["mix_wire"] = wire
     # ---- quality: final mix, then held-out logloss vs the planted-model floor ----
     t = time.perf_counter()
     if world > 1:
         sync_mix(mix_tensors)
-    out["ll"] = None
     if rank == 0:
         eidx, efld, evl, ey, elogit = data["eval"]
         pred = torch.empty(eidx.shape[0], dtype=torch.float32, device=dev)
@@ -381,17 +498,17 @@ def main(argv=None):
                 if ten is not None:
                     ten[sl] = ten[sl][p]
     data = {"eval": None}
-    if rank == 0:
+    if rank == 0 and args.full:
         data["eval"] = gen(args.eval_rows, 999_999, logit=True)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t_gen = time.perf_counter() - t
 
     state = args.state if dev.type == "cuda" else "fp32"
-    main_run = run_schedule(args, ctx, idx, fld, val, y, state, data, metrics)
+    main_run = run_schedule(args, ctx, idx, fld, val, y, state, data, metrics, dump=True)
     alt_state = "fp32" if state == "bf16" else "bf16"
     alt_run = None
-    if dev.type == "cuda" and args.alt_run:
+    if dev.type == "cuda" and args.alt_run and args.full:
         alt_run = run_schedule(args, ctx, idx, fld, val, y, alt_state, data, metrics)
 
     wall = {"gen": round(t_gen, 3)}
@@ -405,7 +522,7 @@ def main(argv=None):
                     **{f"rows_per_s_{alt_state}": alt_run["rows_per_s"] if alt_run else None})
     if rank == 0:
         ll, floor = main_run["ll"], main_run.get("floor")
-        seq_ref = seq_reference(args, world)
+        seq_ref = seq_reference(args, world) if args.full else None
         out = {
             "metric": BASELINE_METRIC,
             "value": round(main_run["rows_per_s"], 1),
@@ -465,7 +582,12 @@ def main(argv=None):
                             else None),
             "rows_trained_per_rank": B * (args.steps + args.warmup),
             "wall_s": wall,
+            "full": bool(args.full),
         }
+        if "dumped" in main_run:
+            out["dumped_outputs"] = main_run["dumped"]
+        if "dumped_state" in main_run:
+            out["dumped_state"] = main_run["dumped_state"]
         if alt_run is not None:
             out[f"value_{alt_state}_state"] = round(alt_run["rows_per_s"], 1)
             out[f"ms_per_step_{alt_state}_state"] = round(alt_run["ms_per_step"], 4)

@@ -39,7 +39,7 @@ def run(world: int, steps: int, a, timeout: int) -> dict:
              "--mix-overlap", str(a.mix_overlap), "--eval-rows", str(a.eval_rows),
              "--resident-batches", str(steps + a.warmup), "--mix-probe", "0", "--alt-run", "0",
              "--state", a.state, "--mix-mode", a.mix_mode, "--mix-state", str(a.mix_state),
-             "--mix-power", str(a.mix_power)]
+             "--mix-power", str(a.mix_power), "--full"]
     if a.dp_lr_power is not None:
         bargs += ["--dp-lr-power", str(a.dp_lr_power)]
     if a.device:

@@ -9,8 +9,8 @@ them: 12,582,912 rows — through
   stream, then ``avg(weight) GROUP BY feature``): ``avgM``;
 
 and reports held-out logloss on bench.py's evaluation rows (262,144 rows, seed 999,999) next to
-the planted-model floor.  The GPU numbers come from bench.py's own JSON (``logloss_heldout``,
-bf16 and fp32 state).  CPU only; ~5 minutes per full pass on 8 cores.
+the planted-model floor.  The GPU numbers come from the JSON of ``bench.py --full``
+(``logloss_heldout``, bf16 and fp32 state).  CPU only; ~5 minutes per full pass on 8 cores.
 
     python benchmarks/ffm_parity_bench_scale.py [--mappers 8] [--rows 12582912]
 """

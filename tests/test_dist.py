@@ -247,7 +247,8 @@ def test_bench_torchrun_cpu_world2():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "512", "--hash-bits", "10",
-           "--mix-every", "1", "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2"]
+           "--mix-every", "1", "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -261,7 +262,8 @@ def test_bench_self_launch_cpu_world2():
     the JSON's value is the whole-job rate of N ranks), and reports the mix cost."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--batch", "512", "--hash-bits", "10", "--mix-every", "1",
-           "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2", "--mix-probe", "2"]
+           "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2", "--mix-probe", "2",
+           "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -273,6 +275,88 @@ def test_bench_self_launch_cpu_world2():
     assert d["config"]["mixes_in_timed_region"] == 2
     assert d["config"]["linear_steps"] == "plain-stores"   # replicas that mix (dp_lin_mode)
     assert d["mix_ms"] > 0 and d["mix_wire_bytes_per_rank"] > 0 and d["mix_bus_gbps"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run times the steps and stops: no held-out logloss, no reference, no probe (those
+    are --full's).  --dump-state writes the state the timed steps left: on the CPU, where the
+    engine is sequential, it equals an independent replay of the same warmup + timed steps on the
+    same rows, and one more timed step changes it.  --dump-outputs writes one more step through
+    the timed path on rows that cannot race (distinct features): the same arrays in every run and
+    whatever the number of timed steps, every probe row trained.  64 MB at most each."""
+    import numpy as np
+
+    from hivemall_amd.io.synthetic import criteo_ffm
+    from hivemall_amd.models.ffm import FFMTrainer, dp_lin_mode
+    from hivemall_amd.ops.ffm import ffm_step
+
+    B, bits, nres, warm = 512, 10, 4, 1
+
+    def run(tag, steps):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+               "--warmup", str(warm), "--batch", str(B), "--hash-bits", str(bits), "--device", "cpu",
+               "--resident-batches", str(nres), "--dump-outputs", str(tmp_path / tag / "out"),
+               "--dump-state", str(tmp_path / tag / "state")]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        arrs = {}
+        for kind, key in (("out", "dumped_outputs"), ("state", "dumped_state")):
+            files = sorted(p.name for p in (tmp_path / tag / kind).iterdir())
+            assert files == sorted(k + ".npy" for k in d[key])
+            arrs[kind] = {f[:-4]: np.load(tmp_path / tag / kind / f) for f in files}
+            for k, a in arrs[kind].items():
+                assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+                assert list(a.shape) == d[key][k]
+            assert sum(a.nbytes for a in arrs[kind].values()) <= 64 << 20
+        return d, arrs["out"], arrs["state"]
+
+    d, out, state = run("a", 2)
+    assert d["full"] is False and d["steps"] == 2 and d["unit"] == "rows/s" and d["dtype"] == "fp32"
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(B / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert d["rows_trained_per_rank"] == B * 3
+    assert d["logloss_heldout"] is None and d["logloss_seq_ref"] is None and "mix_ms" not in d
+    assert not any(k.endswith("_bf16_state") or k.endswith("_bf16") for k in d)
+    assert "eval" not in d["wall_s"]
+    _, out3, state3 = run("c", 3)
+
+    # ---- the state: an independent replay of the benchmark's schedule
+    def replay(steps):
+        idx, fld, val, y = criteo_ffm(B * nres, bits, seed=1000, device=torch.device("cpu"))
+        tr = FFMTrainer(f"-classification -factors 4 -feature_hashing {bits} -num_fields 39 "
+                        f"-seed 31 -batch_size {B}", device="cpu")
+        tr.init_state(1 << bits, 39)
+        for i in range(warm + steps):
+            s = (i % nres) * B
+            ffm_step(tr.state, idx[s:s + B], fld[s:s + B], val[s:s + B], y[s:s + B], tr.hyper,
+                     train=True, lin_mode=dp_lin_mode(1))
+        return tr.state
+
+    assert set(state) == {"feature_rows", "V", "G", "w", "wz", "wn", "bias"}
+    rows = state["feature_rows"].astype(np.int64)
+    assert len(np.unique(rows)) == rows.size == 1 << bits      # the whole small table fits
+    for got, steps in ((state, 2), (state3, 3)):
+        ref = replay(steps)
+        for k in ("V", "G"):
+            np.testing.assert_array_equal(got[k], ref[k][rows].numpy(), err_msg=f"{k} {steps}")
+        for k in ("w", "wz", "wn", "bias"):
+            np.testing.assert_array_equal(got[k], ref[k].numpy(), err_msg=f"{k} {steps}")
+    assert not np.array_equal(state["V"], state3["V"]) and not np.array_equal(state["wn"], state3["wn"])
+
+    # ---- the race-free step: identical whatever the timed steps did
+    assert set(out) == {"feature_rows", "V", "G", "linear_rows", "w", "wz", "wn", "bias", "loss"}
+    for k in out:
+        assert np.array_equal(out[k], out3[k]), k
+    n = (1 << bits) // 39                  # probe rows with 39 distinct features each
+    assert out["loss"].shape == (n,) and (out["loss"] > 0).all()
+    assert out["V"].shape == (n * 39, 39, 4) and out["G"].shape == (n * 39, 39)
+    assert len(np.unique(out["linear_rows"])) == n * 39 == out["linear_rows"].size
+    assert np.array_equal(out["feature_rows"], out["linear_rows"])
+    # every probed feature took its FTRL step (n += g^2) and its AdaGrad steps against the row's
+    # other 38 fields
+    assert (out["wn"] > 0).all() and ((out["G"] > 0).sum(1) >= 38).all()
 
 
 def test_bench_refuses_world_mismatch():
@@ -574,7 +658,8 @@ def test_bench_seq_reference_is_the_cpu_learner_on_the_same_stream():
 
     ref = run(gpus=1, steps=2, warmup=1, batch=512, hash_bits=10, factors=4, resident=2, eval_rows=512)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "512",
-           "--hash-bits", "10", "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2"]
+           "--hash-bits", "10", "--eval-rows", "512", "--device", "cpu", "--resident-batches", "2",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

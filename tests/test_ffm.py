@@ -493,7 +493,7 @@ def test_ffm_gpu_bench_scale_parity_pinned():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gen-device", "cpu",
-                        "--data", "criteo_ffm"],
+                        "--data", "criteo_ffm", "--full"],
                        capture_output=True, text=True, timeout=110, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
