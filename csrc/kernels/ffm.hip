@@ -1129,13 +1129,59 @@ typedef uint32_t u3v_t __attribute__((ext_vector_type(3)));
 // KEEP = 2 also keeps the forward pass's two image reads per slot for the update phase (the image
 // is not written between D and E): 94.2-97.6 vs 92.8-95.4 M rows/s fp32, 153.6-154.3 vs
 // 149.6-150.6 M bf16, same box, interleaved x3 (profiles/r6/keep/bench_keep2_ab.log).
-template <int NS, typename OT, int TPB = 256, int ATOM = 0, int KV = 1, int KEEP = 0, int LT = 0>
+// c . p with every product and every sum rounded on its own, ((c0 p0 + c1 p1) + c2 p2) + c3 p3:
+// what the generic sg32 instantiations compile this expression to under -ffp-contract=fast (two
+// packed multiplies, three adds).  The specialised instantiation contracted it into an fma chain
+// (3e-8 on V after one step; the flag overrides a contract(off) pragma), so PIN passes the
+// products through an empty asm, which nothing is fused across.  tests/test_ffm_specialised.py
+// holds the two forms together.
+template <bool PIN>
+__device__ __forceinline__ float dot4_products_rounded(float4 c, float4 p) {
+    float m0 = c.x * p.x, m1 = c.y * p.y, m2 = c.z * p.z, m3 = c.w * p.w;
+    if constexpr (PIN) asm("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3));
+    return m0 + m1 + m2 + m3;
+}
+
+// CFG (round 7): what a launch fixes, as a bitmask.  0 = nothing: every per-launch constant is a
+// run-time test inside the row loop (the kernel as it was).  SG32_TRAIN = a training launch of the
+// default learner: train, use_linear, lpack and lin_defer set, no global bias (hence no shards),
+// explicit fld and val, no ATOM, no (z, n) atomics on the records (lin_atomic != 1), 32-bit
+// offsets, k <= 4, KEEP = 2; the side table is on exactly when LT is.  dispatch_sg32 picks it when
+// the launch matches.  Each flag below reads "constant if configured, else P.x", so CFG = 0
+// compiles to the generic code.  With SG32_TRAIN the kernel also
+//  - keeps per thread and slot, computed once before the loop: the s_m byte offsets of the slot's
+//    two positions and its transposed-image index in one register, and the predicates s < F F,
+//    a != b and a < b as one bitmask (ab[], okm below);
+//  - takes the wave number from a scalar register, so that the landing zones' M0 values and the
+//    wave-role tests are scalar;
+//  - has the metadata wave publish each feature's block offset i * vfs (s_m[].w; the block
+//    layout has vfs == gfs: V and G of a feature share one block), so phase C multiplies nothing;
+//  - keeps the thread's own image entry (own[], then kcv) in the registers it was written from
+//    in phase B instead of reading it back from the image in D.
+// The arithmetic and its order are those of CFG = 0: variant 11 runs the same launch on CFG = 0 and
+// tests/test_ffm_specialised.py compares the two bitwise.
+constexpr int SG32_TRAIN = 1;
+
+template <int NS, typename OT, int TPB = 256, int ATOM = 0, int KV = 1, int KEEP = 0, int LT = 0, int CFG = 0>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))) void ffm_pipe_sg32_kernel(
     FFMParams P, const int32_t* __restrict__ idx, const int32_t* __restrict__ fld,
     const float* __restrict__ val, const float* __restrict__ y, void* __restrict__ Vt,
     float* __restrict__ Gt, float* __restrict__ w, float* __restrict__ wz, float* __restrict__ wn,
     float* __restrict__ bias, float* __restrict__ pred_out, float* __restrict__ loss_out)
 {
+    constexpr bool SPEC = (CFG & SG32_TRAIN) != 0;
+    static_assert(!SPEC || (ATOM == 0 && KV == 1 && KEEP >= 2 && sizeof(OT) == 4 && TPB == 256),
+                  "SG32_TRAIN: the default fp32 k <= 4 training launch only");
+    // per-launch constants: fixed by the configuration, else the launch's (macros, so that CFG = 0
+    // tests P.x exactly where it did)
+#define c_train (SPEC || P.train)
+#define c_linear (SPEC || P.use_linear)
+#define c_lpack (SPEC || P.lpack)
+#define c_ldefer (SPEC || P.lin_defer)
+#define c_bias (!SPEC && P.use_bias)
+#define c_fld (SPEC || fld)
+#define c_val (SPEC || val)
+#define c_hacc (SPEC ? LT != 0 : P.hacc_on)
     __shared__ __attribute__((aligned(16))) float4 s_rv[NS * TPB * KV]; // V DMA landing zone [q][j][tid]
     __shared__ __attribute__((aligned(16))) float s_rg[NS * TPB];     // G DMA landing zone
     __shared__ __attribute__((aligned(16))) float4 s_t[NS * TPB * KV];  // transposed V image [slot][q]
@@ -1154,10 +1200,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     __shared__ __attribute__((aligned(16))) int s_nh[LT ? 2 : 1][48];   // DMA of the rows' hot indices
     const int F = P.F;
     const int FF = F * F;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = SPEC ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
     constexpr int W_META = 1, W_LIN = 2, W_DMA = 3;
     const OT vfs = (OT)P.fstride * (16u * KV);           // V bytes between features
-    const OT gfs = (OT)P.gstride * 4u;                   // G bytes between features
+    const OT gfs = (OT)P.gstride * 4u;                   // G bytes between features (SPEC: == vfs)
     // (One table replica per XCD, averaged between launches, was measured and removed: +3.1e-3 ..
     // +5.4e-3 vs sequential on the bench stream instead of +2.4e-3; profiles/r5/ffm_xrep_probe.jsonl.)
     const int G = (int)gridDim.x;
@@ -1166,27 +1213,45 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     char* gb = reinterpret_cast<char*>(Gt);
     // linear (z, n) steps by float atomics (FFMParams.lin_atomic; 2 / 3: only the features P.hot
     // flags / does not flag, A/B); one block stores them (exact)
-    const bool latom = ATOM == 0 && !LT && P.lin_atomic == 1 && G > 1;
+    const bool latom = !SPEC && ATOM == 0 && !LT && P.lin_atomic == 1 && G > 1;
     if constexpr (LT != 0) {
         for (int t = tid; t < HD_SIZE; t += TPB) s_hd[t] = make_float2(0.f, 0.f);
     }
     int nh = -1, kh = -1;            // LT, W_LIN lanes: hot index of the next / current row's feature
 
+    // slot s = tid + j TPB is (a, b) = (s / F, s % F); slots past F F are (0, 0).  CFG 0 keeps
+    // a | b << 8.  SPEC keeps a << 4 | b << 10 | t << 16: the byte offsets of s_m[][a], s_m[][b]
+    // and the image index t come out by one shift / mask each (a, b <= 44).  t = b F + a, and for a
+    // slot past F F its own s (< NS TPB, the image's size; such entries are no slot's partner), so
+    // that the image store and both image reads need no s < F F test.
+    // okm, SPEC: bit j = the slot is past F F, bit 8 + j = it is past F F or on the diagonal,
+    // bit 16 + j = a < b.  Phase C moves bit j / 8 + j into the sign of (i_a | i_b), so "valid" and
+    // "live" are one compare each on row data.  (As loop-invariant lane masks the compiler kept
+    // these predicates in 2 scalar registers each and spilled them.)
     int ab[NS];
+    uint32_t okm = 0u;
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
         const int s = tid + j * TPB;
-        ab[j] = s < FF ? (s / F) | ((s % F) << 8) : 0;
+        if constexpr (SPEC) {
+            const int a = s < FF ? s / F : 0, b = s < FF ? s % F : 0;
+            ab[j] = (a << 4) | (b << 10) | ((s < FF ? b * F + a : s) << 16);
+            okm |= (uint32_t)(s >= FF) << j | (uint32_t)(s >= FF || a == b) << (8 + j) | (uint32_t)(a < b) << (16 + j);
+        } else {
+            ab[j] = s < FF ? (s / F) | ((s % F) << 8) : 0;
+        }
     }
-#define SA(j) (ab[j] & 0xFF)
-#define SB(j) (ab[j] >> 8)
+#define SA(j) (SPEC ? (ab[j] >> 4) & 0x3F : ab[j] & 0xFF)
+#define SB(j) (SPEC ? (ab[j] >> 10) & 0x3F : ab[j] >> 8)
+// index of the slot's own entry (b, a) in the transposed image, in KV quads
+#define ST(j) (SPEC ? ab[j] >> 16 : (SB(j) * F + SA(j)) * KV)
 
     auto dma_meta = [&](int bf, int row) {
         if (wave == W_DMA && lane < F && row < P.B) {
             const size_t o = (size_t)row * F + lane;
             __builtin_amdgcn_global_load_lds((glb_ptr_t)(idx + o), (lds_ptr_t)&s_mr[bf][0][0], 4, 0, 0);
-            if (fld) __builtin_amdgcn_global_load_lds((glb_ptr_t)(fld + o), (lds_ptr_t)&s_mr[bf][1][0], 4, 0, 0);
-            if (val) __builtin_amdgcn_global_load_lds((glb_ptr_t)(val + o), (lds_ptr_t)&s_mr[bf][2][0], 4, 0, 0);
+            if (c_fld) __builtin_amdgcn_global_load_lds((glb_ptr_t)(fld + o), (lds_ptr_t)&s_mr[bf][1][0], 4, 0, 0);
+            if (c_val) __builtin_amdgcn_global_load_lds((glb_ptr_t)(val + o), (lds_ptr_t)&s_mr[bf][2][0], 4, 0, 0);
         }
     };
     auto publish_meta = [&](int bf) {
@@ -1194,10 +1259,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             float sq = 0.f;
             if (lane < F) {
                 int ri = s_mr[bf][0][lane];
-                int rf = fld ? s_mr[bf][1][lane] : lane;
-                float rx = val ? __int_as_float(s_mr[bf][2][lane]) : 1.f;
+                int rf = c_fld ? s_mr[bf][1][lane] : lane;
+                float rx = c_val ? __int_as_float(s_mr[bf][2][lane]) : 1.f;
                 if (ri < 0 || ri >= P.num_features || rf < 0 || rf >= P.num_fields) { ri = -1; rx = 0.f; rf = 0; }
-                const int hb = ((ATOM == 2 || (latom && P.lin_atomic >= 2)) && ri >= 0) ? (int)P.hot[ri] : 0;
+                // SPEC (no hot flags): the feature's block offset, one multiply per feature and row
+                // here instead of two per slot in phase C
+                const int hb = SPEC ? (ri >= 0 ? (int)((uint32_t)ri * (uint32_t)vfs) : 0)
+                                    : ((ATOM == 2 || (latom && P.lin_atomic >= 2)) && ri >= 0) ? (int)P.hot[ri] : 0;
                 s_m[bf][lane] = make_int4(ri, rf, __float_as_int(rx), hb);
                 sq = rx * rx;
             }
@@ -1224,6 +1292,31 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     int krep = 0, nrep = 0;
     auto dma_slots = [&](int bf) {
         if constexpr (KEEP) { nlive = 0u; nwr = 0u; nrep = 0; }
+        if constexpr (SPEC) {
+            // slot() with the hoisted invariants: the same offsets, x_a x_b and bits
+            uint32_t eq = 0u;
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {
+                const int4 ma = s_m[bf][SA(j)], mb = s_m[bf][SB(j)];
+                const int both = ma.x | mb.x;                    // < 0: a padded / invalid position
+                const bool ok = (both | (int)(okm << (31 - j))) >= 0;
+                const bool live = (both | (int)(okm << (23 - j))) >= 0;
+                // i * vfs == i * gfs (publish_meta)
+                const OT ib = ok ? (OT)(uint32_t)ma.w : (OT)0, f = ok ? (OT)(uint32_t)mb.y : (OT)0;
+                OT f4 = f * 4u;
+                asm("" : "+v"(f4));      // (else og is derived as ov - 12 f: a 64-bit multiply-add)
+                nov[j] = ib + f * 16u;
+                nog[j] = ib + f4;
+                nxab[j] = live ? __int_as_float(ma.z) * __int_as_float(mb.z) : 0.f;
+                nwr |= (uint32_t)ok << j;
+                eq |= (uint32_t)(ma.x == mb.x || ma.y == mb.y) << j;
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(vb + nov[j]), (lds_ptr_t)(s_rv + j * TPB + wave * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((glb_ptr_t)(gb + nog[j]), (lds_ptr_t)(s_rg + j * TPB + wave * 64), 4, 0, 0);
+            }
+            nlive = nwr & ~(okm >> 8);
+            if (P.defer) nrep = (int)(eq & nwr & (okm >> 16));   // slot_repeats: a < b, both valid
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             OT ov, og;
@@ -1256,18 +1349,22 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     // its older slot DMAs (vmcnt(NLIN)), and for the linear DMA right before its first read in D
     // (vmcnt(2 NS): only the next row's slot DMAs, issued in C, may still be in flight).  Every
     // lane < F issues the DMAs (an invalid feature reads w[0], unused), so the counts are exact.
-    const int nlin = (P.use_linear && P.lin_defer) ? ((P.lpack || !P.train) ? 1 + (LT != 0) : 3) : 0;
+    // SPEC relies on: nlin == 1 + (LT != 0) at compile time (one 16-B record DMA, with LT one
+    // side-table DMA, per lane < F of W_LIN and row, none of them predicated on the feature);
+    // 2 NS slot DMAs per wave and row (KV == 1); with LT one s_nh DMA in phase B, older than the
+    // slot DMAs; and 3 meta DMAs (idx, fld, val) on W_DMA only, which waits with vmcnt(0).
+    const int nlin = (c_linear && c_ldefer) ? ((c_lpack || !c_train) ? 1 + (LT != 0) : 3) : 0;
     auto dma_lin = [&](int bf) {
-        if (P.use_linear && wave == W_LIN && lane < F) {
+        if (c_linear && wave == W_LIN && lane < F) {
             const int i = max(s_m[bf][lane].x, 0);
-            if (P.lpack) {
+            if (c_lpack) {
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin4[bf][0], 16, 0, 0);
                 if constexpr (LT != 0)   // every lane: the wave's DMA count stays exact
                     __builtin_amdgcn_global_load_lds((glb_ptr_t)(P.hacc + HACC_STRIDE * max(nh, 0)), (lds_ptr_t)&s_hacc[bf][0], 16, 0, 0);
                 return;
             }
             __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin[bf][0][0], 4, 0, 0);
-            if (P.train) {
+            if (c_train) {
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(wz, i), (lds_ptr_t)&s_lin[bf][1][0], 4, 0, 0);
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(wn, i), (lds_ptr_t)&s_lin[bf][2][0], 4, 0, 0);
             }
@@ -1300,7 +1397,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     float fg[NS];
     OT fo[NS];
     uint32_t fwd = 0u;
-    const bool bsh = P.use_bias && P.bias_sh;
+    const bool bsh = c_bias && P.bias_sh;
     // A block re-reads the 64 shard lines every bias_every rows (loads of lines the other blocks'
     // atomics keep updating are slow: every row took -w0 from 75 to 40 M rows/s) and adds its own
     // steps since that read (s_bcur) in between; the other blocks' steps arrive with the next read.
@@ -1313,6 +1410,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     for (int cur = 0; row < P.B; row += G, cur ^= 1) {
         const int nxt = cur ^ 1;
         const bool more = row + G < P.B;
+        // (okm stays one register: nothing derived from it is hoisted into scalar lane masks)
+        if constexpr (SPEC) asm volatile("" : "+v"(okm));
         // ---- A: this wave's DMAs have landed, then every wave's ----
         if (wave == W_LIN && nlin == 3) __builtin_amdgcn_s_waitcnt(0x0F73);      // vmcnt(3)
         else if (wave == W_LIN && nlin == 2) __builtin_amdgcn_s_waitcnt(0x0F72); // vmcnt(2)
@@ -1339,6 +1438,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             }
         }
         float cg[NS];
+        float4 own[SPEC ? NS : 1];   // SPEC: the thread's own image entry, as it writes it below
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             cg[j] = s_rg[j * TPB + tid];
@@ -1360,9 +1460,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                     cg[j] = fg[j];
                 }
             }
-            if (tid + j * TPB < FF) {
+            if constexpr (SPEC) {
+                // (a slot past F F reads entry 0 of the image twice in the generic code and its
+                // own entry here: any finite value serves, its x_a x_b is 0 and it is never updated)
+                s_t[ST(j)] = v[0];
+                own[j] = v[0];
+            } else if (tid + j * TPB < FF) {
 #pragma unroll
-                for (int q = 0; q < KV; ++q) s_t[(SB(j) * F + SA(j)) * KV + q] = v[q];
+                for (int q = 0; q < KV; ++q) s_t[ST(j) + q] = v[q];
             }
         }
         fwd = 0u;
@@ -1387,10 +1492,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             const int4 m = s_m[cur][lane];
             mi = m.x;
             mx = __int_as_float(m.z);
-            lw = P.lpack ? s_lin4[cur][lane].x : s_lin[cur][0][lane];
+            lw = c_lpack ? s_lin4[cur][lane].x : s_lin[cur][0][lane];
             if (latom) lw = lin_w(P, s_lin4[cur][lane]);
             if constexpr (LT != 0) {
-                if (P.hacc_on && mi >= 0 && kh >= 0) {
+                if (c_hacc && mi >= 0 && kh >= 0) {
                     // hot: the side table as DMA'd (the other blocks' flushed steps) + this block's own
                     const float4 a = s_hacc[cur][lane];
                     const float2 d = s_hd[kh];
@@ -1423,10 +1528,12 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             float dot = 0.f;
 #pragma unroll
             for (int q = 0; q < KV; ++q) {
-                const float4 pv = s_t[(s < FF ? s : 0) * KV + q];
-                const float4 cv = s_t[(SB(j) * F + SA(j)) * KV + q];
+                const float4 pv = s_t[(SPEC || s < FF ? s : 0) * KV + q];
+                float4 cv;
+                if constexpr (SPEC) cv = own[j];         // the thread's own entry, held since B
+                else cv = s_t[ST(j) + q];
                 if constexpr (KEEP >= 2) { kpv[j][q] = pv; kcv[j][q] = cv; }
-                dot += cv.x * pv.x + cv.y * pv.y + cv.z * pv.z + cv.w * pv.w;
+                dot += dot4_products_rounded<SPEC>(cv, pv);
             }
             part += dot * xab[j];
         }
@@ -1444,16 +1551,16 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
         int rdup = 0;
 #pragma unroll
         for (int q = 0; q < TPB / 64; ++q) { p += s_red[q]; rdup |= s_rep[q]; }
-        if (P.use_bias) p += bsh ? s_bias[0] : bias_w0(P, bias);
+        if (c_bias) p += bsh ? s_bias[0] : bias_w0(P, bias);
         const float kappa = row_loss(P, row, p, y, pred_out, loss_out);
 
         // ---- E: updates (a multi-hot row is deferred to ffm_row_kernel) ----
         // the shards read at this row's B lack only this row's own step (wave 0 waits for its
         // atomics at every phase A, so all earlier ones had landed)
         if (bre && tid == 0) { s_bcur[0] = 0.f; s_bcur[1] = 0.f; }
-        if (P.train && rdup && P.defer) {
+        if (c_train && rdup && P.defer) {
             defer_row(P, row);
-        } else if (P.train) {
+        } else if (c_train) {
             const float ks = kappa * scale * scale;
 #pragma unroll
             for (int j = 0; j < NS; ++j) {
@@ -1477,7 +1584,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                     // KEEP >= 2: the two image reads of the forward pass, kept in registers (the
                     // image is not written between D and E)
                     const float4 pv = KEEP >= 2 ? kpv[j][q] : s_t[s * KV + q];
-                    const float4 cv = KEEP >= 2 ? kcv[j][q] : s_t[(SB(j) * F + SA(j)) * KV + q];
+                    const float4 cv = KEEP >= 2 ? kcv[j][q] : s_t[ST(j) + q];
                     o0[q] = f2{cv.x, cv.y};
                     o1[q] = f2{cv.z, cv.w};
                     const f2 p0 = f2{pv.x, pv.y}, p1 = f2{pv.z, pv.w};
@@ -1521,9 +1628,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             // store of the diagonal / dead slots too was slower: 72.4-72.7 vs 74.9-75.5 M,
             // profiles/r4/ffm_skip_diagonal_ab.log.)
             if (mi >= 0) {
-                if (P.use_linear) {   // FTRL-proximal on the DMA'd (w, z, n)
-                    const float lz = hot ? hz : (P.lpack ? s_lin4[cur][lane].y : s_lin[cur][1][lane]);
-                    const float ln = hot ? hn : (P.lpack ? s_lin4[cur][lane].z : s_lin[cur][2][lane]);
+                if (c_linear) {   // FTRL-proximal on the DMA'd (w, z, n)
+                    const float lz = hot ? hz : (c_lpack ? s_lin4[cur][lane].y : s_lin[cur][1][lane]);
+                    const float ln = hot ? hn : (c_lpack ? s_lin4[cur][lane].z : s_lin[cur][2][lane]);
                     const float g = kappa * mx * scale;
                     const float n1 = ln + g * g;
                     const float z1 = lz + g - (sqrtf(n1) - sqrtf(ln)) / P.alpha * lw;
@@ -1537,7 +1644,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                         LW(w, mi) = w1;
                     } else if (latom && (P.lin_atomic == 1 || (P.lin_atomic == 2) == (s_m[cur][lane].w != 0))) {
                         lin_add(P, w, mi, g, ln, n1, lw);
-                    } else if (P.lpack) {
+                    } else if (c_lpack) {
                         *reinterpret_cast<float4*>(&LW(w, mi)) = make_float4(w1, z1, n1, s_lin4[cur][lane].w);
                     } else {
                         LW(wz, mi) = z1;
@@ -1546,7 +1653,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                     }
                 }
             }
-            if (P.use_bias && tid == 0) {
+            if (c_bias && tid == 0) {
                 if (bsh) bias_update_sh(P, kappa, s_bias[1], s_bias[2], P.bias_sh + (blockIdx.x % P.bias_s) * 32, s_bcur);
                 else bias_update(P, kappa, bias);
             }
@@ -1570,7 +1677,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
         bar_raw();
         // Lanes 2e, 2e + 1 add z, n of entry e (one 8-B run per entry and instruction: 67 -> 76 M
         // rows/s against one lane adding both)
-        if (P.hacc_on)
+        if (c_hacc)
             for (int t = tid; t < 2 * P.nhot; t += TPB) {
                 const float2 d = s_hd[t >> 1];
                 if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + HACC_STRIDE * (t >> 1) + (t & 1), (t & 1) ? d.y : d.x);
@@ -1578,6 +1685,15 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     }
 #undef SA
 #undef SB
+#undef ST
+#undef c_train
+#undef c_linear
+#undef c_lpack
+#undef c_ldefer
+#undef c_bias
+#undef c_fld
+#undef c_val
+#undef c_hacc
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2040,7 +2156,7 @@ int dispatch_sg12(const FFMParams& P, const int32_t* idx, const int32_t* fld, co
     int blocks = default_blocks(P.B, grid, 256 * 8 * 8);
     if (blocks <= 0) return 0;
     FFMParams Q = P;
-    Q.hacc_on = P.lin_atomic == 4 && P.nhot <= HD12_SIZE && blocks > 1 && !wide && variant != 9 && variant != 10;
+    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && P.nhot <= HD12_SIZE && blocks > 1 && !wide && variant != 9 && variant != 10;
     if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID12);
     if (Q.hacc_on) {
         hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
@@ -2087,7 +2203,7 @@ int dispatch_sg32(const FFMParams& P, const int32_t* idx, const int32_t* fld, co
         if (blocks <= 0) return 0;
         // lin_atomic 4 as for k = 4 below (the 16 KB of block sums still leave one block per CU)
         FFMParams Q = P;
-        Q.hacc_on = P.lin_atomic == 4 && blocks > 1 && !wide && variant != 6 && variant != 9;
+        Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && blocks > 1 && !wide && variant != 6 && variant != 9;
         if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID);
         if (Q.hacc_on) {
             hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
@@ -2123,15 +2239,31 @@ int dispatch_sg32(const FFMParams& P, const int32_t* idx, const int32_t* fld, co
     // lin_atomic 4: the side table for a launch of more than one block (one block stores the
     // records in row order: the sequential engine)
     FFMParams Q = P;
-    Q.hacc_on = P.lin_atomic == 4 && blocks > 1 && !wide && variant != 6 && variant != 8 && variant != 9 && variant != 10;
+    // (the side table needs lin_defer: without the deferred wait, nlin == 0, phase F would read
+    // the DMA'd hot indices with no wait before it)
+    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && blocks > 1 && !wide && variant != 6 && variant != 8 &&
+                variant != 9 && variant != 10;
     if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID);
     if (Q.hacc_on) {
         hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
         HM_LAUNCH_RET_IF_ERR();
     }
+    // The default kernel choice (variant 0) of a training launch of the default learner takes the
+    // instantiation specialised for it (SG32_TRAIN above); anything else — predict, -w0, separate
+    // linear arrays, implicit fields or values, record atomics, wide tables, the A/B variants — the
+    // generic one.  Variant 11 = the same launch (LT, KEEP, grid) on the generic instantiation.
+    const bool spec = variant == 0 && !wide && P.train && P.use_linear && P.lpack && P.lin_defer &&
+                      !P.use_bias && fld && val && P.lin_atomic != 1 &&
+                      (size_t)P.fstride * 16 == (size_t)P.gstride * 4;
 #define HM_P32(NSV) do { \
         if (wide) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint64_t>), dim3(blocks), dim3(256), 0, stream, \
                                      P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); \
+        else if (spec && Q.hacc_on) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2, 1, SG32_TRAIN>), \
+                                                  dim3(blocks), dim3(256), 0, stream, Q, idx, fld, val, y, V, G, w, wz, \
+                                                  wn, bias, pred, loss); \
+        else if (spec) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2, 0, SG32_TRAIN>), \
+                                          dim3(blocks), dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
+                                          bias, pred, loss); \
         else if (variant == 6) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 1>), dim3(blocks), \
                                                   dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
                                                   bias, pred, loss); \
@@ -2269,7 +2401,9 @@ int launch_deferred(FFMParams P, const int32_t* idx, const int32_t* fld, const f
 // for bf16, 3 = ffm_pipe_kernel for fp32 (per-element G), 6 = ffm_pipe_sg32_kernel with every
 // slot update added by float atomics (no lost update; the learner's early-training ramp,
 // models/ffm.py RAMP_*; G-only atomics were measured as variant 7 and removed: the full gap at
-// 12 M rows/s, profiles/r4/ffm_g_atomic_bench_ab.log).  Measured and removed: 512-thread sg32
+// 12 M rows/s, profiles/r4/ffm_g_atomic_bench_ab.log); 11 = the default sg32 kernel choice (same
+// LT, KEEP and grid) forced onto the generic instantiation, CFG = 0, where the default takes the
+// one specialised for a training launch (SG32_TRAIN; round 7, k <= 4 only).  Measured and removed: 512-thread sg32
 // blocks (75.7-76.1 vs 75.6 M rows/s, profiles/r4/ffm_512_thread_ab.log); a paired-slot sg32
 // kernel holding each (a, b) / (b, a) slot pair in one thread's registers instead of a transposed
 // LDS image (4 rows in flight per CU instead of 2): 58.1-58.4 vs 74.9-75.5 M rows/s — the (b, a)
