@@ -2,8 +2,17 @@
 (kernel-expanded Passive-Aggressive).
 
 Reference behaviour: Hivemall recommend/SlimUDTF, classifier/KernelExpansionPassiveAggressiveUDTF,
-classifier/KPAPredictUDAF.  Both are small, per-item /
-per-example sequential learners and run on the host.
+classifier/KPAPredictUDAF.
+
+``train_slim`` has two engines (``-engine auto|native|torch``).  ``native`` keeps the ratings as
+one CSC matrix of rating vectors and runs ``ops.slim``: a Gram-build kernel over sparse columns
+(no dense ``users x K`` matrix) and a coordinate-descent kernel with one wave per item and the
+item's fp64 Gram matrix in LDS (``csrc/kernels/slim.hip``; ``csrc/host/slim_cpu.cpp`` on a CPU
+device).  ``SLIM.fit_csc`` is its columnar entry point; ``SLIM.fit`` (the SQL surface) groups
+the rows as upstream does and hands them over.  ``torch`` is the batched torch descent over
+NumPy Gram matrices, ``slim_cd_batched``, the reference the native engine is tested against.
+Both are fp64 throughout and follow the update and coordinate order of upstream's residual
+loop.  ``train_kpa`` is a small per-example sequential learner and runs on the host.
 """
 from __future__ import annotations
 
@@ -14,8 +23,8 @@ import numpy as np
 import pandas as pd
 
 from ..registry import udaf
-from ..utils.options import opt
-from .base import Learner
+from ..utils.options import UDFArgumentException, opt
+from .base import Learner, log
 
 SLIM_OPTS = [
     opt("l1", None, 0.001, float, "L1 regularization"),
@@ -23,6 +32,9 @@ SLIM_OPTS = [
     opt("iters", "iterations", 30, int, "Coordinate-descent sweeps", aliases=("iter",)),
     opt("eps", None, 1e-4, float, "Convergence threshold on the max weight change"),
     opt("disable_cv", None, None, str, "Accepted"),
+    opt("engine", None, "auto", str, "[engine] native (Gram-build and coordinate-descent kernels, "
+        "ops/slim.py) | torch (batched torch descent over NumPy Gram matrices) | auto (native when "
+        "its library loads)"),
 ]
 
 
@@ -97,14 +109,53 @@ def _slim_cd_chunk(Gs, bs, l1: float, l2: float, iters: int, eps: float, device=
     return w.cpu().numpy()
 
 
+def _object_array(seq) -> np.ndarray:
+    out = np.empty(len(seq), dtype=object)
+    for k, v in enumerate(seq):
+        out[k] = v
+    return out
+
+
+def _padded_neighbours(nbr, n: int) -> np.ndarray:
+    """``nbr`` as int32 [n, K] with -1 padding, from such an array or one sequence per item."""
+    if isinstance(nbr, np.ndarray) and nbr.ndim == 2:
+        out = nbr.astype(np.int32)
+    else:
+        seqs = [np.asarray(s, dtype=np.int32).reshape(-1) for s in nbr]
+        out = np.full((len(seqs), max((len(s) for s in seqs), default=0)), -1, dtype=np.int32)
+        for t, s in enumerate(seqs):
+            out[t, :len(s)] = s
+    if out.shape[0] != n:
+        raise ValueError(f"train_slim: {out.shape[0]} neighbour lists for {n} targets")
+    return out
+
+
 class SLIM(Learner):
     """For every item i: min_w ½||r_i − Σ_j w_j r_j||² + ½λ2||w||² + λ1||w||₁, w ≥ 0, over the
     item's kNN neighbours j (coordinate descent with soft thresholding)."""
     NAME = "train_slim"
     OPTIONS = SLIM_OPTS
 
+    def engine(self) -> str:
+        """``-engine`` resolved: "native" (ops.slim: the gfx950 kernels on a cuda device, their
+        C++ twins on the CPU) or "torch" (slim_cd_batched).  ``auto`` takes native when the
+        library it needs loads."""
+        e = str(self.cl["engine"]).lower()
+        if e not in ("auto", "native", "torch"):
+            raise UDFArgumentException(f"{self.NAME}: -engine must be auto, native or torch, got '{e}'")
+        if e != "auto":
+            return e
+        from .. import _native
+
+        try:
+            _native.hip() if self.device.type == "cuda" else _native.host()
+        except Exception as ex:  # no compiler / no library on this machine
+            log.info("%s: native library unavailable (%s); -engine torch", self.NAME, ex)
+            return "torch"
+        return "native"
+
     def fit(self, i_col, ri_col, knn_col, j_col, rj_col):
-        c = self.cl
+        engine = self.engine()
         groups: dict = defaultdict(lambda: {"ri": None, "nb": {}})
         for i, ri, knn, j, rj in zip(i_col, ri_col, knn_col, j_col, rj_col):
             g = groups[i]
@@ -115,6 +166,128 @@ class SLIM(Learner):
             if knn:
                 for jj, rr in dict(knn).items():
                     g["nb"].setdefault(jj, dict(rr))
+        if engine == "native":
+            return self._fit_groups_native(groups)
+        return self._fit_groups_torch(groups)
+
+    def _fit_groups_native(self, groups: dict):
+        """The grouped rows as one CSC matrix (every distinct rating vector stored once, user ids
+        mapped to dense int32 and sorted per column), then ``fit_csc``."""
+        uix: dict = {}
+        cols: dict = defaultdict(list)            # item id -> [(vector, column)]
+        labels, lens, rws, vls = [], [], [], []
+
+        def column(item, vec) -> int:
+            for known, cid in cols[item]:
+                if known == vec:
+                    return cid
+            r = np.fromiter((uix.setdefault(u, len(uix)) for u in vec), dtype=np.int64, count=len(vec))
+            v = np.fromiter((float(x) for x in vec.values()), dtype=np.float64, count=len(vec))
+            o = np.argsort(r, kind="stable")
+            cid = len(labels)
+            cols[item].append((vec, cid))
+            labels.append(item)
+            lens.append(len(vec))
+            rws.append(r[o])
+            vls.append(v[o])
+            return cid
+
+        targets, nbl = [], []
+        for i, g in groups.items():
+            ri = g["ri"] or {}
+            nbs = [j for j in g["nb"] if j != i]
+            if not ri or not nbs:
+                continue
+            targets.append(column(i, ri))
+            nbl.append([column(j, g["nb"][j]) for j in nbs])
+        if not targets:
+            self.table = pd.DataFrame([], columns=["i", "nn", "w"])
+            return self
+        if len(uix) > np.iinfo(np.int32).max:
+            raise UDFArgumentException(f"{self.NAME}: more than 2^31 - 1 distinct users")
+        colptr = np.zeros(len(labels) + 1, dtype=np.int64)
+        np.cumsum(lens, out=colptr[1:])
+        R = (colptr, np.concatenate(rws).astype(np.int32), np.concatenate(vls))
+        return self.fit_csc(R, targets, nbl, item_ids=labels)
+
+    def fit_csc(self, R, targets, nbr, item_ids=None):
+        """Columnar entry point: ``R`` holds the rating vectors as the columns of a
+        ``utils.matrix.CSCMatrix`` (or a ``(colptr, rows, vals)`` triple; row = user), ``targets[t]``
+        is the column of item t's own vector and ``nbr[t]`` the columns of its neighbours (a
+        padded ``[n, K]`` array with ``-1`` for "none", or one sequence per item).
+        ``item_ids[col]`` names a column in the model table (default: the column number).
+
+        Items are solved in neighbourhood-size-sorted chunks of bounded Gram bytes: ``slim_gram``
+        then ``slim_cd`` on the learner's device; items with more than ``ops.slim.KMAX``
+        neighbours take ``slim_gram`` and the torch descent.  ``-engine torch`` runs the same
+        Gram build and ``slim_cd_batched``."""
+        import torch
+
+        from ..ops import slim as S
+        from ..utils.matrix import CSCMatrix
+
+        c = self.cl
+        l1, l2, iters, eps = float(c["l1"]), float(c["l2"]), int(c["iters"]), float(c["eps"])
+        native_cd = self.engine() == "native"
+        if isinstance(R, CSCMatrix):
+            R = (R.indptr, R.indices, R.values)
+        try:
+            colptr = torch.as_tensor(np.ascontiguousarray(R[0], dtype=np.int64))
+            rows = torch.as_tensor(np.ascontiguousarray(R[1], dtype=np.int32))
+            vals = torch.as_tensor(np.ascontiguousarray(R[2], dtype=np.float64))
+            targets = np.asarray(targets, dtype=np.int32).reshape(-1)
+        except (TypeError, ValueError) as ex:
+            raise ValueError(f"{self.NAME}: fit_csc wants numeric (colptr, rows, vals) and targets: {ex}") from ex
+        n = len(targets)
+        nb = _padded_neighbours(nbr, n)
+        n_cols = S.check_csc(colptr, rows, vals)
+        labels = np.arange(n_cols) if item_ids is None else _object_array(item_ids)
+        if len(labels) != n_cols:
+            raise ValueError(f"{self.NAME}: item_ids has {len(labels)} entries for {n_cols} columns")
+        if n and nb.shape[1] and (nb.max() >= n_cols or nb.min() < -1):
+            raise ValueError(f"{self.NAME}: neighbour column ids must be -1 or in 0..{n_cols - 1}")
+        # the item's own column is no neighbour of its (fit drops j == i)
+        nb = np.where(nb == targets[:, None], -1, nb)
+        # neighbours left-aligned, order kept
+        nb = np.take_along_axis(nb, np.argsort(nb < 0, axis=1, kind="stable"), axis=1)
+        size = (nb >= 0).sum(1)
+        W = np.zeros(nb.shape)
+        dev = self.device
+        colptr, rows, vals = colptr.to(dev), rows.to(dev), vals.to(dev)
+        order = np.argsort(size, kind="stable")
+        order = order[size[order] > 0]
+        s, m = 0, len(order)
+        while s < m:
+            e = s + 1
+            kc = int(size[order[s]])
+            while e < m:
+                k_next = max(kc, int(size[order[e]]))
+                if (e + 1 - s) * k_next * k_next * 8 > _SLIM_CHUNK_BYTES:
+                    break
+                if native_cd and kc <= S.KMAX < k_next:
+                    break                       # larger items form chunks of their own
+                kc = k_next
+                e += 1
+            idx = order[s:e]
+            G, b = S.slim_gram(colptr, rows, vals, torch.from_numpy(targets[idx]).to(dev),
+                               torch.from_numpy(np.ascontiguousarray(nb[idx, :kc])).to(dev), check=False)
+            if native_cd and kc <= S.KMAX:
+                w = S.slim_cd(G, b, l1, l2, iters, eps).cpu().numpy()
+            else:
+                Gn, bn = G.cpu().numpy(), b.cpu().numpy()
+                ks = size[idx]
+                w = slim_cd_batched([Gn[t, :k, :k] for t, k in enumerate(ks)],
+                                    [bn[t, :k] for t, k in enumerate(ks)], l1, l2, iters, eps, dev)
+            W[idx, :kc] = w[:, :kc]
+            s = e
+        t, k = np.nonzero((W != 0) & (nb >= 0))       # row-major: items in order, neighbours in order
+        # .tolist(): Python scalars, so that pandas infers the id columns as it does from row tuples
+        self.table = pd.DataFrame({"i": labels[targets[t]].tolist(), "nn": labels[nb[t, k]].tolist(),
+                                   "w": W[t, k]}, columns=["i", "nn", "w"])
+        return self
+
+    def _fit_groups_torch(self, groups: dict):
+        c = self.cl
         items, nbl, Gs, bs = [], [], [], []
         for i, g in groups.items():
             ri = g["ri"] or {}
