@@ -216,7 +216,9 @@ __global__ __launch_bounds__(64) void linear_train_kernel(
             for (int64_t k = s + lane; k < e; k += 64) {
                 const float x = val ? val[k] : 1.f;
                 const int i = idx[k];
-                if (i >= 0 && i < dims) sqp += x * x;
+                if (i < 0 || i >= dims) continue;
+                sqp += x * x;
+                if (k >= s + 64) T[i] = 1;      // the first chunk was marked with the cached indices
             }
             sq = hm::wave_sum(sqp);
             for (int l = 0; l < L; ++l) {

@@ -375,7 +375,10 @@ HM_HD RowCoef row_rule(const Params& P, float p, float y, float var, float sq, f
             // logistic regression on a [0,1] target: gradient = target - sigmoid(p)
             const float s = sigmoidf(p);
             const float g = y - s;
-            c.loss = -(y * logf(fmaxf(s, 1e-7f)) + (1.f - y) * logf(fmaxf(1.f - s, 1e-7f)));
+            // cross-entropy, each term clamped at -log(1e-7); -log(s) = softplus(-p) and
+            // -log(1 - s) = softplus(p): 1.f - s itself loses every digit once s rounds to 1
+            const float cl = 16.118095651f;
+            c.loss = y * fminf(log1pexpf(-p), cl) + (1.f - y) * fminf(log1pexpf(p), cl);
             c.update = g != 0.f;
             c.dloss = -g;
             break;
