@@ -8,7 +8,9 @@ SURVEY.md §2.3.7, K11).
 Device design: a mini-batch of documents is flattened to (doc, word, count) non-zeros and the
 E-step runs vectorised over all of them (gather of exp E[log β] columns, scatter-add per
 document) — on the GPU it is a handful of fused torch kernels per inner iteration.  The
-vocabulary is dictionary-encoded on the host (words are strings in SQL).
+vocabulary is dictionary-encoded on the host (words are strings in SQL).  LDA's E-step and, under
+``train_plsa -engine native``, pLSA's per-document EM and P(w|z) update run as single gfx950
+kernels instead (csrc/kernels/lda.hip, csrc/kernels/plsa.hip).
 
 Model tables: LDA ``(label int, word string, lambda float)``; pLSA ``(label, word, prob)``.
 """
@@ -264,17 +266,30 @@ PLSA_OPTS = [
     opt("iters", "iterations", 10, int, "Epochs", aliases=("iter",)),
     opt("eps", None, 1e-1, float, "Perplexity convergence threshold"),
     opt("mini_batch_size", "batch_size", 128, int, "Documents per mini-batch"),
+    opt("max_inner_iters", None, 50, int, "[engine] Per-document EM iteration cap"),
+    opt("engine", None, "auto", str, "[engine] native (per-document EM and P(w|z) update kernels, "
+        "ops/plsa.py; at most 256 topics) | torch (tensor ops, one EM loop per mini-batch) | auto "
+        "(native on a GPU when its library loads, torch on the CPU)"),
     opt("seed", None, -1, int, "Seed"),
 ]
 
 
 class PLSA(Learner):
+    """Incremental-EM pLSA.  Two engines (``-engine auto|native|torch``):
+
+    ``torch`` runs a mini-batch's EM as tensor ops and stops the whole batch when the
+    batch-wide mean change of P(z|d) falls below ``-delta``.  ``native`` (ops/plsa.py) runs each
+    document's EM inside one kernel, stops every document on its own change (the upstream rule),
+    and updates P(w|z) with a deterministic kernel sequence; the corpus and every mini-batch's
+    word index are built once per ``fit`` and an epoch has no host synchronisation.  With one
+    document per mini-batch the two stopping rules coincide."""
     NAME = "train_plsa"
     OPTIONS = PLSA_OPTS
 
     def __init__(self, options=None, device=None, **kw):
         super().__init__(options, device, **kw)
         self.K = int(self.cl["topics"])
+        self._engine = self.engine()
         self.vocab = _Vocab()
         self.pwz: torch.Tensor | None = None       # [K, V]
         self.gen = torch.Generator(device="cpu").manual_seed(self.seed)
@@ -287,6 +302,31 @@ class PLSA(Learner):
             extra = torch.full((self.K, V - self.pwz.shape[1]), 1e-6, device=self.device)
             self.pwz = torch.cat([self.pwz, extra], 1)
             self.pwz /= self.pwz.sum(1, keepdim=True)
+
+    def engine(self) -> str:
+        """``-engine`` resolved: "native" (ops.plsa: the gfx950 kernels on a cuda device, their
+        C++ twins on the CPU) or "torch".  ``auto`` is torch on the CPU and, on a cuda device,
+        native when the kernel library loads and ``-topics`` fits its 256 lanes."""
+        from ..ops import plsa as P
+
+        e = str(self.cl["engine"]).lower()
+        if e not in ("auto", "native", "torch"):
+            raise UDFArgumentException(f"{self.NAME}: -engine must be auto, native or torch, got '{e}'")
+        if e == "native" and not 1 <= self.K <= P.KMAX:
+            raise UDFArgumentException(f"{self.NAME}: -engine native holds 1..{P.KMAX} topics, got {self.K}")
+        if e != "auto":
+            return e
+        if self.device.type != "cuda":
+            return "torch"
+        if not 1 <= self.K <= P.KMAX:
+            log.info("%s: %d topics exceed the native engine's %d; -engine torch", self.NAME, self.K, P.KMAX)
+            return "torch"
+        try:
+            _native.hip()
+        except Exception as ex:  # no compiler / no library on this machine
+            log.info("%s: native library unavailable (%s); -engine torch", self.NAME, ex)
+            return "torch"
+        return "native"
 
     def _doc_em(self, doc, w, c, B, iters=50):
         pzd = torch.full((B, self.K), 1.0 / self.K, device=self.device)
@@ -304,18 +344,58 @@ class PLSA(Learner):
         q = q / q.sum(1, keepdim=True).clamp_min(1e-30)
         return pzd, q
 
+    def _csr(self, rows):
+        """The rows flattened once: (doc_off int64 numpy [D+1], wid int32 [N], cnt f32 [N])."""
+        _, w, cnt = _flatten(rows, self.device)
+        ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rows], out=ptr[1:])
+        return ptr, w.to(torch.int32), cnt
+
+    def _fit_native(self, rows) -> "PLSA":
+        from ..ops import plsa as P
+
+        c, dev = self.cl, self.device
+        V = self.pwz.shape[1]
+        bs = int(c["mini_batch_size"])
+        ptr, w_all, c_all = self._csr(rows)
+        batches = []                                # fixed slices: indexed and validated once
+        for s in range(0, len(rows), bs):
+            e = min(len(rows), s + bs)
+            a, b = int(ptr[s]), int(ptr[e])
+            if a == b:
+                continue
+            doc_off = torch.from_numpy((ptr[s:e + 1] - a).astype(np.int32)).to(dev)
+            wid, cnt = w_all[a:b], c_all[a:b]
+            P.check_doc_batch(doc_off, wid, cnt, V)
+            perm, word_off, uniq = P.batch_index(wid)
+            batches.append((doc_off, wid, cnt, word_off, perm, uniq))
+        if not batches:
+            return self
+        scratch = P.mstep_scratch(max(b[5].numel() for b in batches), V, self.K, dev)
+        pwzT = self.pwz.T.contiguous()
+        delta, cap, alpha = float(c["delta"]), int(c["max_inner_iters"]), float(c["alpha"])
+        for ep in range(int(c["iters"])):
+            for doc_off, wid, cnt, word_off, perm, uniq in batches:
+                _, contrib, _ = P.plsa_doc_em(doc_off, wid, cnt, pwzT, delta, cap, check=False)
+                P.plsa_mstep(word_off, perm, uniq, contrib, alpha, pwzT, scratch, check=False)
+        self.pwz = pwzT.T.contiguous()
+        return self
+
     def fit(self, docs) -> "PLSA":
         c = self.cl
         rows = self.vocab.encode(list(docs), add=True)
         self._grow(len(self.vocab.words))
+        if self._engine == "native":
+            return self._fit_native(rows)
         bs = int(c["mini_batch_size"])
         a = float(c["alpha"])
+        cap = int(c["max_inner_iters"])
         for ep in range(int(c["iters"])):
             for s in range(0, len(rows), bs):
                 doc, w, cnt = _flatten(rows[s:s + bs], self.device)
                 if doc.numel() == 0:
                     continue
-                _, q = self._doc_em(doc, w, cnt, len(rows[s:s + bs]))
+                _, q = self._doc_em(doc, w, cnt, len(rows[s:s + bs]), cap)
                 nwz = torch.zeros_like(self.pwz).index_add_(1, w, (q * cnt[:, None]).T)
                 upd = nwz / nwz.sum(1, keepdim=True).clamp_min(1e-30)
                 self.pwz = (1 - a) * self.pwz + a * upd
@@ -330,8 +410,16 @@ class PLSA(Learner):
 
     def transform(self, docs) -> np.ndarray:
         rows = self.vocab.encode(list(docs), add=False)
+        if self._engine == "native":
+            from ..ops import plsa as P
+
+            ptr, wid, cnt = self._csr(rows)
+            doc_off = torch.from_numpy(ptr.astype(np.int32)).to(self.device)
+            pzd, _, _ = P.plsa_doc_em(doc_off, wid, cnt, self.pwz.T.contiguous(), float(self.cl["delta"]),
+                                      int(self.cl["max_inner_iters"]))
+            return pzd.cpu().numpy()
         doc, w, cnt = _flatten(rows, self.device)
-        pzd, _ = self._doc_em(doc, w, cnt, len(rows))
+        pzd, _ = self._doc_em(doc, w, cnt, len(rows), int(self.cl["max_inner_iters"]))
         return pzd.cpu().numpy()
 
 
