@@ -4,7 +4,10 @@ knn/{similarity,distance,lsh}/*.java, tools/EachTopKUDTF.java).
 Row-wise functions take Hivemall feature arrays (``"name:value"`` strings, or plain numeric
 arrays for the dense forms).  ``pairwise_cosine`` / ``topk_similar`` are the batched device
 paths: an MFMA-backed GEMM (torch.matmul on ROCm -> hipBLASLt) over L2-normalised dense
-matrices followed by ``torch.topk``.
+matrices followed by ``torch.topk``.  ``topk_similar_csc`` is their sparse sibling: exact fp64
+cosine top-k between the columns of a CSC matrix of any height (``ops/knn_sparse.py``: one
+workgroup per query column, the candidates' dots accumulated in LDS; no dense matrix), which
+is what ``train_slim`` needs as its neighbour lists.  ``cosine_knn`` is its SQL surface.
 """
 from __future__ import annotations
 
@@ -266,3 +269,87 @@ def topk_similar(X: torch.Tensor, Y: torch.Tensor | None = None, k: int = 10):
     if Y is None:
         S.fill_diagonal_(-float("inf"))
     return torch.topk(S, min(k, S.shape[1]), dim=1)
+
+
+def topk_similar_csc(R, k: int, queries=None, device=None):
+    """Exact cosine top-k between the columns of a sparse matrix: (scores fp64 [n, k], indices
+    int32 [n, k]) of the ``k`` most similar columns for every column in ``queries`` (default:
+    all), best first, the column itself excluded, ``0.0`` / ``-1`` where fewer than ``k`` columns
+    share a row with it.  Ties go to the smaller column id.
+
+    ``R`` is a ``utils.matrix.CSCMatrix`` or a ``(colptr, rows, vals)`` triple (rows strictly
+    increasing inside a column); columns are the vectors, of any height.  Runs
+    ``ops.knn_sparse.knn_cols`` on ``device`` (default: the GPU when there is one)."""
+    from ..models.base import resolve_device
+    from ..ops.knn_sparse import knn_cols
+    from ..utils.matrix import CSCMatrix
+
+    n_rows = None
+    if isinstance(R, CSCMatrix):
+        n_rows = R.n_rows
+        R = (R.indptr, R.indices, R.values)
+    dev = resolve_device(device)
+    try:
+        colptr = torch.as_tensor(np.ascontiguousarray(R[0], dtype=np.int64))
+        rows = torch.as_tensor(np.ascontiguousarray(R[1], dtype=np.int32))
+        vals = torch.as_tensor(np.ascontiguousarray(R[2], dtype=np.float64))
+        q = None if queries is None else torch.as_tensor(
+            np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)).to(dev)
+    except (TypeError, ValueError) as ex:
+        raise ValueError(f"topk_similar_csc wants a numeric (colptr, rows, vals) and queries: {ex}") from ex
+    idx, score = knn_cols(colptr.to(dev), rows.to(dev), vals.to(dev), k, q, n_rows=n_rows)
+    return score, idx
+
+
+@udtf("cosine_knn", per_row=False, cols=("key", "rank", "other", "similarity"))
+def cosine_knn(k, key, feature, value, session=None):
+    """cosine_knn(const int k, key, feature, double value) -> table (key, rank, other, similarity):
+    for every key, its k most cosine-similar other keys over their sparse (feature, value)
+    vectors, rank 1 = best; only keys that share a feature are candidates, ties go to the key
+    seen first. Extension (not in upstream Hivemall): item-item similarity + each_top_k in one
+    native step (ops/knn_sparse.py)."""
+    import pandas as pd
+
+    from ..models.base import resolve_device
+    from ..ops.knn_sparse import knn_cols
+    from ..utils.options import UDFArgumentException
+
+    kk = k[0] if isinstance(k, (list, tuple, np.ndarray, pd.Series)) and len(k) else k
+    try:
+        kk = int(kk)
+    except (TypeError, ValueError):
+        raise UDFArgumentException(f"cosine_knn: k must be a constant int, got {kk!r}") from None
+    if not 1 <= kk <= 128:
+        raise UDFArgumentException(f"cosine_knn: k must be in 1..128, got {kk}")
+    out_cols = ["key", "rank", "other", "similarity"]
+    keep = [t for t in zip(key, feature, value) if not any(x is None for x in t)]
+    if not keep:
+        return pd.DataFrame([], columns=out_cols)
+    kc, labels = pd.factorize(np.asarray([t[0] for t in keep], dtype=object))
+    fc, feats = pd.factorize(np.asarray([t[1] for t in keep], dtype=object))
+    try:
+        v = np.asarray([float(t[2]) for t in keep], dtype=np.float64)
+    except (TypeError, ValueError) as ex:
+        raise UDFArgumentException(f"cosine_knn: value must be numeric: {ex}") from None
+    if len(feats) > np.iinfo(np.int32).max or len(labels) > np.iinfo(np.int32).max:
+        raise UDFArgumentException("cosine_knn: more than 2^31 - 1 distinct keys or features")
+    o = np.lexsort((fc, kc))
+    kc, fc, v = kc[o], fc[o], v[o]
+    dup = (kc[1:] == kc[:-1]) & (fc[1:] == fc[:-1])
+    if dup.any():
+        d = int(np.flatnonzero(dup)[0])
+        raise UDFArgumentException(f"cosine_knn: duplicate (key, feature) pair "
+                                   f"({labels[kc[d]]!r}, {feats[fc[d]]!r})")
+    colptr = np.zeros(len(labels) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(kc, minlength=len(labels)), out=colptr[1:])
+    dev = resolve_device(None if session is None else session.device)
+    idx, score = knn_cols(torch.from_numpy(colptr).to(dev), torch.from_numpy(fc.astype(np.int32)).to(dev),
+                          torch.from_numpy(v).to(dev), kk, n_rows=len(feats))
+    idx, score = idx.cpu().numpy(), score.cpu().numpy()
+    q, r = np.nonzero(idx >= 0)                      # row-major: keys in order, best first
+    return pd.DataFrame({"key": labels[q].tolist(), "rank": (r + 1).tolist(),
+                         "other": labels[idx[q, r]].tolist(), "similarity": score[q, r]},
+                        columns=out_cols)
+
+
+cosine_knn.wants_session = True

@@ -8,8 +8,9 @@ classifier/KPAPredictUDAF.
 one CSC matrix of rating vectors and runs ``ops.slim``: a Gram-build kernel over sparse columns
 (no dense ``users x K`` matrix) and a coordinate-descent kernel with one wave per item and the
 item's fp64 Gram matrix in LDS (``csrc/kernels/slim.hip``; ``csrc/host/slim_cpu.cpp`` on a CPU
-device).  ``SLIM.fit_csc`` is its columnar entry point; ``SLIM.fit`` (the SQL surface) groups
-the rows as upstream does and hands them over.  ``torch`` is the batched torch descent over
+device).  ``SLIM.fit_csc`` is its columnar entry point (with ``knn=K`` it finds the neighbours
+itself: ``ops.knn_sparse``); ``SLIM.fit`` (the SQL surface) groups the rows as upstream does and
+hands them over.  ``torch`` is the batched torch descent over
 NumPy Gram matrices, ``slim_cd_batched``, the reference the native engine is tested against.
 Both are fp64 throughout and follow the update and coordinate order of upstream's residual
 loop.  ``train_kpa`` is a small per-example sequential learner and runs on the host.
@@ -210,12 +211,14 @@ class SLIM(Learner):
         R = (colptr, np.concatenate(rws).astype(np.int32), np.concatenate(vls))
         return self.fit_csc(R, targets, nbl, item_ids=labels)
 
-    def fit_csc(self, R, targets, nbr, item_ids=None):
+    def fit_csc(self, R, targets, nbr=None, item_ids=None, knn=None):
         """Columnar entry point: ``R`` holds the rating vectors as the columns of a
         ``utils.matrix.CSCMatrix`` (or a ``(colptr, rows, vals)`` triple; row = user), ``targets[t]``
         is the column of item t's own vector and ``nbr[t]`` the columns of its neighbours (a
         padded ``[n, K]`` array with ``-1`` for "none", or one sequence per item).
         ``item_ids[col]`` names a column in the model table (default: the column number).
+        Without ``nbr``, ``knn=K`` takes every target's ``K`` nearest columns by cosine
+        (``ops.knn_sparse.knn_cols`` on the learner's device) as its neighbours.
 
         Items are solved in neighbourhood-size-sorted chunks of bounded Gram bytes: ``slim_gram``
         then ``slim_cd`` on the learner's device; items with more than ``ops.slim.KMAX``
@@ -229,7 +232,9 @@ class SLIM(Learner):
         c = self.cl
         l1, l2, iters, eps = float(c["l1"]), float(c["l2"]), int(c["iters"]), float(c["eps"])
         native_cd = self.engine() == "native"
+        n_rows = None
         if isinstance(R, CSCMatrix):
+            n_rows = R.n_rows
             R = (R.indptr, R.indices, R.values)
         try:
             colptr = torch.as_tensor(np.ascontiguousarray(R[0], dtype=np.int64))
@@ -239,8 +244,16 @@ class SLIM(Learner):
         except (TypeError, ValueError) as ex:
             raise ValueError(f"{self.NAME}: fit_csc wants numeric (colptr, rows, vals) and targets: {ex}") from ex
         n = len(targets)
-        nb = _padded_neighbours(nbr, n)
+        if nbr is None and knn is None:
+            raise ValueError(f"{self.NAME}: fit_csc wants the neighbours (nbr) or their number (knn)")
         n_cols = S.check_csc(colptr, rows, vals)
+        if nbr is None:
+            from ..ops.knn_sparse import knn_cols
+
+            dev = self.device
+            nbr = knn_cols(colptr.to(dev), rows.to(dev), vals.to(dev), knn,
+                           torch.from_numpy(targets).to(dev), n_rows=n_rows)[0].cpu().numpy()
+        nb = _padded_neighbours(nbr, n)
         labels = np.arange(n_cols) if item_ids is None else _object_array(item_ids)
         if len(labels) != n_cols:
             raise ValueError(f"{self.NAME}: item_ids has {len(labels)} entries for {n_cols} columns")
