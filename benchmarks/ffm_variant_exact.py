@@ -1,7 +1,8 @@
 """One block (-grid 1) of an FFM kernel variant vs the sequential CPU engine on field-disjoint
-criteo_like rows (test_ffm_gpu_single_block_is_exactly_sequential's setup), for A/B variants.
+criteo_like rows (test_ffm_gpu_single_block_is_exactly_sequential's setup), for the live variants
+(hivemall_amd.ops.ffm.VARIANTS).
 
-    python benchmarks/ffm_variant_exact.py 0 9
+    python benchmarks/ffm_variant_exact.py 0 11
 """
 import json
 import os

@@ -60,7 +60,9 @@ struct FFMParams {
     float eta0, eps, lambda_v;
     float alpha, beta, lambda1, lambda2;
     float min_target, max_target;  // regression clipping of the prediction
-    const uint8_t* hot;            // per-feature flags (ffm_pipe_sg32_kernel ATOM = 2), or null
+    // Unused 8 bytes, where the retired per-feature hot flags' pointer was: they keep every later
+    // member's kernel-argument offset, and with it the device code of the measured kernels, unchanged.
+    const void* reserved;
     // Multi-hot rows (two features of one field, or one feature twice: two slots of the row are
     // the same (feature, field) address).  A row updates each address once with its summed
     // gradient (docs/compat.md).  The pipelined kernels detect such rows in their forward pass
@@ -75,12 +77,13 @@ struct FFMParams {
     // one 16-B store per feature instead of three scattered 4-B ones into three more lines.
     long long lstride;
     int lpack;
-    // lin_atomic (lpack records, ATOM = 0 pipelined kernels, grid > 1): each row ADDS its FTRL
-    // steps dz, g^2 to the record's (z, n) with float atomics instead of storing {w, z, n}, and w is
-    // derived as f(z, n) where it is read (ffm_lin_derive_kernel refreshes the stored w after the
-    // launch).  Round 6: a host model of W rows in flight (benchmarks/ffm_hogwild_sim.py) put 79 %
-    // of the same-stream gap on lost linear updates (+3.86e-3 -> +0.81e-3 at W = 1024 with only
-    // the linear (z, n) added, nothing else changed; the V / G slots' lost updates the rest).
+    // lin_atomic (lpack records): 0 = every row stores its {w, z, n} records (a concurrent row's step
+    // to the same feature is lost), 4 = the hot features' (z, n) in a side table (below).  Round 6: a
+    // host model of W rows in flight (benchmarks/ffm_hogwild_sim.py) put 79 % of the same-stream gap
+    // on lost linear updates (+3.86e-3 -> +0.81e-3 at W = 1024 with only the linear (z, n) added,
+    // nothing else changed; the V / G slots' lost updates the rest).  Measured and removed: modes
+    // 1 - 3, float atomics on the records themselves (8.7 M rows/s vs 93 M with plain stores,
+    // profiles/r6/linhot/).
     int lin_atomic;
     const int32_t* hidx;           // lin_atomic 4: hot index of each feature (-1: cold), [num_features]
     const int32_t* hot_id;         // lin_atomic 4: feature of each hot index, [nhot]
@@ -150,20 +153,6 @@ __device__ __forceinline__ void bias_update_sh(const FFMParams& P, float g, floa
     atomicAdd(sh + 1, g * g);
     acc[0] += dz;
     acc[1] += g * g;
-}
-
-// lin_atomic: the weight of a DMA'd {w, z, n, _} record is f(z, n) (its stored w lags: rows add
-// to (z, n) only); a record never stepped (n = 0) keeps its stored w
-__device__ __forceinline__ float lin_w(const FFMParams& P, float4 r) {
-    return r.z > 0.f ? ftrl_weight(r.y, r.z, P.alpha, P.beta, P.lambda1, P.lambda2) : r.x;
-}
-
-// lin_atomic: the row's FTRL step of feature i as two no-return float atomics on its record's
-// (z, n): dz = g - sigma w (the host engine's association: z + (g - sigma w)), dn = g^2
-__device__ __forceinline__ void lin_add(const FFMParams& P, float* w, int i, float g, float n0,
-                                        float n1, float wcur) {
-    atomicAdd(&LW(w, i) + 1, g - (sqrtf(n1) - sqrtf(n0)) / P.alpha * wcur);
-    atomicAdd(&LW(w, i) + 2, g * g);
 }
 
 // lin_atomic 4 (template LT of the pipelined kernels): the linear FTRL state (z, n) of the
@@ -551,7 +540,10 @@ __global__ __launch_bounds__(256) void ffm_row_kernel(
 
 
 // ---------------------------------------------------------------------------------------------
-// Lean packed kernel (K <= 4, packed V|G slots): the shipped kernel for the headline shape.
+// Lean packed kernel (K <= 4, packed per-element V|G slots, fp32 state; bf16 state takes
+// ffm_pipe_kernel below, which keeps the bf16 items of this list).  Measured and removed: this
+// kernel on bf16 state (variant 2), 88 vs 101 M rows/s for the pipeline, same box
+// (profiles/ffm_r2/ab_pipe_v1.log ... ab_pipe_v5_dpp.log).
 //
 // Counters of ffm_packed_kernel on MI355X (profiles/ffm_pmc_packed_r2b.json) show the row loop
 // is bound by vector-instruction ISSUE, not by memory: 3,976 VALU wave-instructions per row
@@ -596,27 +588,19 @@ __device__ __forceinline__ uint32_t pack_sr_hi(f2 v, uint32_t ra, uint32_t rb) {
 
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return __builtin_amdgcn_alignbit(x, x, 32 - r); }
 
-template <bool BF>
-struct LeanIO {
-    // raw slot: bf16 -> uint4 {v01, v23, g01, g23}; fp32 -> V float4 + G float4
-    using Raw = typename std::conditional<BF, uint4, float4[2]>::type;
-    using Img = typename std::conditional<BF, uint2, float4>::type;   // V in the LDS image
-};
-
-template <bool BF, int NS>
+template <int NS>
 __global__ __launch_bounds__(256) void ffm_lean_kernel(
     FFMParams P, const int32_t* __restrict__ idx, const int32_t* __restrict__ fld,
     const float* __restrict__ val, const float* __restrict__ y, void* __restrict__ VG,
     float* __restrict__ w, float* __restrict__ wz, float* __restrict__ wn,
     float* __restrict__ bias, float* __restrict__ pred_out, float* __restrict__ loss_out)
 {
-    using Img = typename LeanIO<BF>::Img;
-    constexpr uint32_t SLOT_B = BF ? 16u : 32u;          // bytes per packed slot
+    constexpr uint32_t SLOT_B = 32u;                    // bytes per packed slot: V float4 | G float4
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int F = P.F;
     const int FF = F * F;
-    Img* s_t = reinterpret_cast<Img*>(smem);                                     // FF (transposed)
-    int4* s_m = reinterpret_cast<int4*>(smem + (size_t)FF * sizeof(Img));      // F x {i, f, x, -}
+    float4* s_t = reinterpret_cast<float4*>(smem);                               // FF (transposed)
+    int4* s_m = reinterpret_cast<int4*>(smem + (size_t)FF * sizeof(float4));   // F x {i, f, x, -}
     float* s_red = reinterpret_cast<float*>(s_m + F);                           // 16
     const int tid = threadIdx.x;
     const uint32_t nfld = (uint32_t)P.fstride;
@@ -630,7 +614,6 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
         sa[j] = s < FF ? s / F : 0;
         sb[j] = s < FF ? s % F : 0;
     }
-    const uint32_t tid_h = (uint32_t)tid * 0x9E3779B1u;
 
     for (int row = blockIdx.x; row < P.B; row += gridDim.x) {
         // ---- row metadata -> LDS {i, f, x}; instance-wise L2 norm (the block sum's barrier
@@ -661,7 +644,6 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
 
         // ---- gather (branch-free): own raw slot -> registers, own V -> transposed LDS image.
         //      Dead slots (a == b, padding) load slot 0 and get x_a x_b = 0. ----
-        uint4 q[NS];
         float4 qv[NS], qg[NS];
         uint32_t off[NS];
         float xab[NS];
@@ -674,14 +656,9 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
             live[j] = sa[j] != sb[j] && ma.x >= 0 && mb.x >= 0;
             off[j] = live[j] ? ((uint32_t)ma.x * nfld + (uint32_t)mb.y) * SLOT_B : 0u;
             xab[j] = live[j] ? __int_as_float(ma.z) * __int_as_float(mb.z) : 0.f;
-            if constexpr (BF) {
-                q[j] = *reinterpret_cast<const uint4*>(vg + off[j]);
-                s_t[sb[j] * F + sa[j]] = make_uint2(q[j].x, q[j].y);
-            } else {
-                qv[j] = *reinterpret_cast<const float4*>(vg + off[j]);
-                qg[j] = *reinterpret_cast<const float4*>(vg + off[j] + 16u);
-                s_t[sb[j] * F + sa[j]] = qv[j];
-            }
+            qv[j] = *reinterpret_cast<const float4*>(vg + off[j]);
+            qg[j] = *reinterpret_cast<const float4*>(vg + off[j] + 16u);
+            s_t[sb[j] * F + sa[j]] = qv[j];
         }
         const bool rdup = __syncthreads_or(rep) != 0;
 
@@ -691,14 +668,8 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const int s = tid + j * 256;
-            float d;
-            if constexpr (BF) {
-                const uint2 pv = s_t[s < FF ? s : 0];
-                d = dot2_bf16(q[j].x, pv.x, dot2_bf16(q[j].y, pv.y, 0.f));
-            } else {
-                const float4 pv = s_t[s < FF ? s : 0];
-                d = qv[j].x * pv.x + qv[j].y * pv.y + qv[j].z * pv.z + qv[j].w * pv.w;
-            }
+            const float4 pv = s_t[s < FF ? s : 0];
+            const float d = qv[j].x * pv.x + qv[j].y * pv.y + qv[j].z * pv.z + qv[j].w * pv.w;
             part += d * xab[j];
         }
         part *= 0.5f * scale * scale;
@@ -716,23 +687,14 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
             const float ks = kappa * scale * scale;
             const f2 lam = {P.lambda_v, P.lambda_v}, eps = {P.eps, P.eps};
             const f2 meta = {-P.eta0, -P.eta0};
-            const uint32_t hrow = P.seed ^ ((uint32_t)row * 0x85EBCA77u);
 #pragma unroll
             for (int j = 0; j < NS; ++j) {
                 const int s = tid + j * 256;
                 const f2 coef = {ks * xab[j], ks * xab[j]};
-                f2 o0, o1, g0, g1, p0, p1;
-                if constexpr (BF) {
-                    const uint2 pv = s_t[s < FF ? s : 0];
-                    o0 = bf2_to_f2(q[j].x); o1 = bf2_to_f2(q[j].y);
-                    g0 = bf2_to_f2(q[j].z); g1 = bf2_to_f2(q[j].w);
-                    p0 = bf2_to_f2(pv.x);   p1 = bf2_to_f2(pv.y);
-                } else {
-                    const float4 pv = s_t[s < FF ? s : 0];
-                    o0 = f2{qv[j].x, qv[j].y}; o1 = f2{qv[j].z, qv[j].w};
-                    g0 = f2{qg[j].x, qg[j].y}; g1 = f2{qg[j].z, qg[j].w};
-                    p0 = f2{pv.x, pv.y};       p1 = f2{pv.z, pv.w};
-                }
+                const float4 pv = s_t[s < FF ? s : 0];
+                f2 o0 = f2{qv[j].x, qv[j].y}, o1 = f2{qv[j].z, qv[j].w};
+                f2 g0 = f2{qg[j].x, qg[j].y}, g1 = f2{qg[j].z, qg[j].w};
+                const f2 p0 = f2{pv.x, pv.y}, p1 = f2{pv.z, pv.w};
                 const f2 d0 = coef * p0 + lam * o0, d1 = coef * p1 + lam * o1;
                 g0 = g0 + d0 * d0;
                 g1 = g1 + d1 * d1;
@@ -741,22 +703,9 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
                 const f2 r1 = {__builtin_amdgcn_rsqf(t1.x), __builtin_amdgcn_rsqf(t1.y)};
                 o0 = o0 + meta * d0 * r0;
                 o1 = o1 + meta * d1 * r1;
-                if constexpr (BF) {
-                    // one hash per slot, full-rate 24-bit multiply; 8 rotated 16-bit windows
-                    uint32_t h = hrow + tid_h + (uint32_t)j * 0x6A09E667u;
-                    h ^= h >> 16;
-                    h = __umul24(h, 0x2C1B3Du) ^ (h >> 11);
-                    h ^= h >> 15;
-                    const uint4 st = make_uint4(pack_sr_hi(o0, h, rotl32(h, 16)),
-                                                pack_sr_hi(o1, rotl32(h, 8), rotl32(h, 24)),
-                                                pack_sr_hi(g0, rotl32(h, 4), rotl32(h, 20)),
-                                                pack_sr_hi(g1, rotl32(h, 12), rotl32(h, 28)));
-                    if (live[j]) *reinterpret_cast<uint4*>(vg + off[j]) = st;
-                } else {
-                    if (live[j]) {
-                        *reinterpret_cast<float4*>(vg + off[j]) = make_float4(o0.x, o0.y, o1.x, o1.y);
-                        *reinterpret_cast<float4*>(vg + off[j] + 16u) = make_float4(g0.x, g0.y, g1.x, g1.y);
-                    }
+                if (live[j]) {
+                    *reinterpret_cast<float4*>(vg + off[j]) = make_float4(o0.x, o0.y, o1.x, o1.y);
+                    *reinterpret_cast<float4*>(vg + off[j] + 16u) = make_float4(g0.x, g0.y, g1.x, g1.y);
                 }
             }
             if (P.use_linear && mi >= 0) {
@@ -775,7 +724,7 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
 
 
 // ---------------------------------------------------------------------------------------------
-// Pipelined kernel (packed per-element V|G, K <= 4; bf16 or fp32 state): the next row's 1,482
+// Pipelined kernel (packed per-element V|G, K <= 4, bf16 state): the next row's 1,482
 // slot gathers fly into LDS by LDS-DMA (global_load_lds_dwordx4: no VGPR destination) while the
 // current row computes.
 //
@@ -798,8 +747,9 @@ __global__ __launch_bounds__(256) void ffm_lean_kernel(
 // Polling the DMA targets instead of vmcnt(0) (so no wave waits on the previous row's stores),
 // with an LDS hand-over of slots shared by consecutive rows, was measured no faster (101.1-101.6 M
 // rows/s default vs 98.8-100.8 M polled, profiles/ffm_poll_r2/bench_ab_corrected.log) and removed.
-// BF = false: the same pipeline over fp32 packed slots (32 B: V float4 | G float4; two 16-B DMAs
-// per slot; LDS 77.6 KB at NS = 6 -> 2 blocks/CU; opt-in HM_FFM_VARIANT=3).
+// Measured and removed: the same pipeline over fp32 packed slots (variant 3), 52.5 vs the lean
+// kernel's 51.2 M rows/s but held-out logloss +0.019 vs sequential at 500 K rows against +0.010
+// (profiles/ffm_r2/fp32_pipe_ab.log).
 __device__ __forceinline__ void bar_raw() {
     __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS writes are done
     __builtin_amdgcn_s_barrier();
@@ -810,17 +760,16 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 
-template <int NS, bool BF = true>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2))) void ffm_pipe_kernel(
+template <int NS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void ffm_pipe_kernel(
     FFMParams P, const int32_t* __restrict__ idx, const int32_t* __restrict__ fld,
     const float* __restrict__ val, const float* __restrict__ y, void* __restrict__ VG,
     float* __restrict__ w, float* __restrict__ wz, float* __restrict__ wn,
     float* __restrict__ bias, float* __restrict__ pred_out, float* __restrict__ loss_out)
 {
-    constexpr uint32_t SLOT_B = BF ? 16u : 32u;                        // bytes per packed slot
-    using Img = typename std::conditional<BF, uint2, float4>::type;   // V in the transposed image
-    __shared__ __attribute__((aligned(16))) uint4 s_raw[NS * 256 * (BF ? 1 : 2)];   // slot DMA landing zone
-    __shared__ __attribute__((aligned(16))) Img s_t[NS * 256];        // transposed V image
+    constexpr uint32_t SLOT_B = 16u;                                  // bytes per packed slot
+    __shared__ __attribute__((aligned(16))) uint4 s_raw[NS * 256];    // slot DMA landing zone
+    __shared__ __attribute__((aligned(16))) uint2 s_t[NS * 256];      // transposed V image
     // F <= 45 (F*F <= 2048): per-field arrays of 48; total LDS 40,736 B at NS = 6 -> 4 blocks/CU
     __shared__ __attribute__((aligned(16))) int4 s_m[2][48];          // validated meta {i, f, x}
     __shared__ __attribute__((aligned(16))) int s_mr[2][3][48];       // raw meta DMA {idx, fld, val}
@@ -893,15 +842,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
             uint32_t off;
             float xab;
             slot(bf, j, off, xab);
-            if constexpr (BF) {
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(vg + off),
-                                                 (lds_ptr_t)(s_raw + j * 256 + wave * 64), 16, 0, 0);
-            } else {   // V half, then G half: rows 2j and 2j + 1 of the landing zone
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(vg + off),
-                                                 (lds_ptr_t)(s_raw + (2 * j) * 256 + wave * 64), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(vg + off + 16u),
-                                                 (lds_ptr_t)(s_raw + (2 * j + 1) * 256 + wave * 64), 16, 0, 0);
-            }
+            __builtin_amdgcn_global_load_lds((glb_ptr_t)(vg + off),
+                                             (lds_ptr_t)(s_raw + j * 256 + wave * 64), 16, 0, 0);
         }
     };
     // wave W_LIN, lanes < F with a valid feature: DMA of w, z, n of the row in buffer bf
@@ -941,22 +883,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
         bar_raw();
         // ---- B: raw -> registers, V -> transposed image; meta(row + G) -> s_m[nxt] ----
         uint4 q[NS];
-        float4 qv[NS], qg[NS];   // fp32 state
-        if constexpr (!BF) {
 #pragma unroll
-            for (int j = 0; j < NS; ++j) {
-                const uint4 a = s_raw[(2 * j) * 256 + tid], b = s_raw[(2 * j + 1) * 256 + tid];
-                qv[j] = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
-                qg[j] = make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
-            }
+        for (int j = 0; j < NS; ++j) q[j] = s_raw[j * 256 + tid];
 #pragma unroll
-            for (int j = 0; j < NS; ++j) s_t[SB(j) * F + SA(j)] = qv[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < NS; ++j) q[j] = s_raw[j * 256 + tid];
-#pragma unroll
-            for (int j = 0; j < NS; ++j) s_t[SB(j) * F + SA(j)] = make_uint2(q[j].x, q[j].y);
-        }
+        for (int j = 0; j < NS; ++j) s_t[SB(j) * F + SA(j)] = make_uint2(q[j].x, q[j].y);
         uint32_t off[NS];
         float xab[NS];
         uint32_t live = 0u, wr = 0u;
@@ -989,14 +919,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
 #pragma unroll
         for (int j = 0; j < NS; ++j) {
             const int s = tid + j * 256;
-            float d;
-            if constexpr (BF) {
-                const uint2 pv = s_t[s < FF ? s : 0];
-                d = dot2_bf16(q[j].x, pv.x, dot2_bf16(q[j].y, pv.y, 0.f));
-            } else {
-                const float4 pv = s_t[s < FF ? s : 0];
-                d = qv[j].x * pv.x + qv[j].y * pv.y + qv[j].z * pv.z + qv[j].w * pv.w;
-            }
+            const uint2 pv = s_t[s < FF ? s : 0];
+            const float d = dot2_bf16(q[j].x, pv.x, dot2_bf16(q[j].y, pv.y, 0.f));
             part += d * xab[j];
         }
         part *= 0.5f * scale * scale;
@@ -1025,18 +949,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
             for (int j = 0; j < NS; ++j) {
                 const int s = tid + j * 256;
                 const f2 coef = {ks * xab[j], ks * xab[j]};
-                f2 o0, o1, g0, g1, p0, p1;
-                if constexpr (BF) {
-                    const uint2 pv = s_t[s < FF ? s : 0];
-                    o0 = bf2_to_f2(q[j].x); o1 = bf2_to_f2(q[j].y);
-                    g0 = bf2_to_f2(q[j].z); g1 = bf2_to_f2(q[j].w);
-                    p0 = bf2_to_f2(pv.x);   p1 = bf2_to_f2(pv.y);
-                } else {
-                    const float4 pv = s_t[s < FF ? s : 0];
-                    o0 = f2{qv[j].x, qv[j].y}; o1 = f2{qv[j].z, qv[j].w};
-                    g0 = f2{qg[j].x, qg[j].y}; g1 = f2{qg[j].z, qg[j].w};
-                    p0 = f2{pv.x, pv.y};       p1 = f2{pv.z, pv.w};
-                }
+                const uint2 pv = s_t[s < FF ? s : 0];
+                f2 o0 = bf2_to_f2(q[j].x), o1 = bf2_to_f2(q[j].y);
+                f2 g0 = bf2_to_f2(q[j].z), g1 = bf2_to_f2(q[j].w);
+                const f2 p0 = bf2_to_f2(pv.x), p1 = bf2_to_f2(pv.y);
                 // diagonal slots: coef = 0 and lambda = 0 -> d = 0, V and G unchanged, and the
                 // stochastic rounding of a value already in bf16 is exact
                 const float lj = (live >> j & 1u) ? P.lambda_v : 0.f;
@@ -1049,13 +965,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
                 const f2 r1 = {__builtin_amdgcn_rsqf(t1.x), __builtin_amdgcn_rsqf(t1.y)};
                 o0 = o0 + meta * d0 * r0;
                 o1 = o1 + meta * d1 * r1;
-                if constexpr (!BF) {
-                    if (wr >> j & 1u) {
-                        *reinterpret_cast<float4*>(vg + off[j]) = make_float4(o0.x, o0.y, o1.x, o1.y);
-                        *reinterpret_cast<float4*>(vg + off[j] + 16u) = make_float4(g0.x, g0.y, g1.x, g1.y);
-                    }
-                    continue;
-                }
                 // this thread's row hash, re-keyed per slot: each 16-bit window stays uniform
                 const uint32_t h = rotl32(hrow, 5 * j + 1) ^ (0x9E3779B9u * (uint32_t)(j + 1));
                 const uint4 st = make_uint4(pack_sr_hi(o0, h, rotl32(h, 16)),
@@ -1070,10 +979,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BF ? 4 : 2)
             if (wave == 0 && lane < F) {
                 const int pi = s_m[cur][lane].x;
                 if (pi >= 0) {
-                    for (int f = P.num_fields; f < (int)nfld; ++f) {
+                    for (int f = P.num_fields; f < (int)nfld; ++f)
                         *reinterpret_cast<uint4*>(vg + ((uint32_t)pi * nfld + (uint32_t)f) * SLOT_B) = make_uint4(0u, 0u, 0u, 0u);
-                        if (!BF) *reinterpret_cast<uint4*>(vg + ((uint32_t)pi * nfld + (uint32_t)f) * SLOT_B + 16u) = make_uint4(0u, 0u, 0u, 0u);
-                    }
                 }
             }
             if (mi >= 0) {
@@ -1118,7 +1025,8 @@ typedef uint32_t u3v_t __attribute__((ext_vector_type(3)));
 // KV = 16-B quads per slot: 1 for k <= 4 (the 896-B blocks above), 2 for k <= 8 (32-B V slots,
 // 1,536-B blocks; the landing zone and the image double, 107 KB of LDS at 39 fields: one block
 // per CU, launched with 512 threads so that each SIMD still holds two waves).
-// KEEP >= 1 (round 6; the default is 2, variant 10 = 1, variant 9 = 0 for A/B): each slot's offsets, x_a x_b and live / written / repeat bits are derived
+// KEEP >= 1 (round 6; the k <= 4 default is 2, k = 8 takes 1, the 64-bit-offset and ATOM = 1
+// launches 0): each slot's offsets, x_a x_b and live / written / repeat bits are derived
 // from the row metadata ONCE, in phase C (next to that row's DMA issue), and kept in registers
 // for the row's B / D / E phases; the other phases re-read both metadata entries of every slot from
 // LDS, and the (b)-side reads of 16-B entries conflict where b wraps from F - 1 to 0 inside a
@@ -1145,8 +1053,7 @@ __device__ __forceinline__ float dot4_products_rounded(float4 c, float4 p) {
 // CFG (round 7): what a launch fixes, as a bitmask.  0 = nothing: every per-launch constant is a
 // run-time test inside the row loop (the kernel as it was).  SG32_TRAIN = a training launch of the
 // default learner: train, use_linear, lpack and lin_defer set, no global bias (hence no shards),
-// explicit fld and val, no ATOM, no (z, n) atomics on the records (lin_atomic != 1), 32-bit
-// offsets, k <= 4, KEEP = 2; the side table is on exactly when LT is.  dispatch_sg32 picks it when
+// explicit fld and val, no ATOM, 32-bit offsets, k <= 4, KEEP = 2; the side table is on exactly when LT is.  dispatch_sg32 picks it when
 // the launch matches.  Each flag below reads "constant if configured, else P.x", so CFG = 0
 // compiles to the generic code.  With SG32_TRAIN the kernel also
 //  - keeps per thread and slot, computed once before the loop: the s_m byte offsets of the slot's
@@ -1211,9 +1118,6 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     const int bid = (int)blockIdx.x;
     char* vb = reinterpret_cast<char*>(Vt);
     char* gb = reinterpret_cast<char*>(Gt);
-    // linear (z, n) steps by float atomics (FFMParams.lin_atomic; 2 / 3: only the features P.hot
-    // flags / does not flag, A/B); one block stores them (exact)
-    const bool latom = !SPEC && ATOM == 0 && !LT && P.lin_atomic == 1 && G > 1;
     if constexpr (LT != 0) {
         for (int t = tid; t < HD_SIZE; t += TPB) s_hd[t] = make_float2(0.f, 0.f);
     }
@@ -1262,10 +1166,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                 int rf = c_fld ? s_mr[bf][1][lane] : lane;
                 float rx = c_val ? __int_as_float(s_mr[bf][2][lane]) : 1.f;
                 if (ri < 0 || ri >= P.num_features || rf < 0 || rf >= P.num_fields) { ri = -1; rx = 0.f; rf = 0; }
-                // SPEC (no hot flags): the feature's block offset, one multiply per feature and row
-                // here instead of two per slot in phase C
-                const int hb = SPEC ? (ri >= 0 ? (int)((uint32_t)ri * (uint32_t)vfs) : 0)
-                                    : ((ATOM == 2 || (latom && P.lin_atomic >= 2)) && ri >= 0) ? (int)P.hot[ri] : 0;
+                // SPEC: the feature's block offset, one multiply per feature and row here instead of
+                // two per slot in phase C
+                const int hb = SPEC && ri >= 0 ? (int)((uint32_t)ri * (uint32_t)vfs) : 0;
                 s_m[bf][lane] = make_int4(ri, rf, __float_as_int(rx), hb);
                 sq = rx * rx;
             }
@@ -1493,7 +1396,6 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             mi = m.x;
             mx = __int_as_float(m.z);
             lw = c_lpack ? s_lin4[cur][lane].x : s_lin[cur][0][lane];
-            if (latom) lw = lin_w(P, s_lin4[cur][lane]);
             if constexpr (LT != 0) {
                 if (c_hacc && mi >= 0 && kh >= 0) {
                     // hot: the side table as DMA'd (the other blocks' flushed steps) + this block's own
@@ -1602,7 +1504,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                 fg[j] = gs;
                 fo[j] = ov;
                 fwd |= 1u << j;
-                if (ATOM == 1 || (ATOM == 2 && s_m[cur][SA(j)].w != 0)) {
+                if (ATOM == 1) {
                     // concurrent rows' updates of one slot all land (no read-modify-write race)
                     if (live >> j & 1u) {
                         float* vp = reinterpret_cast<float*>(vb + ov);
@@ -1638,12 +1540,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
                     if (LT && hot) {
                         const float2 d = s_hd[kh];
                         s_hd[kh] = make_float2(d.x + (g - (sqrtf(n1) - sqrtf(ln)) / P.alpha * lw), d.y + g * g);
-                    } else if (ATOM == 1 || (ATOM == 2 && s_m[cur][lane].w != 0)) {
+                    } else if (ATOM == 1) {
                         atomicAdd(&LW(wz, mi), z1 - lz);
                         atomicAdd(&LW(wn, mi), g * g);
                         LW(w, mi) = w1;
-                    } else if (latom && (P.lin_atomic == 1 || (P.lin_atomic == 2) == (s_m[cur][lane].w != 0))) {
-                        lin_add(P, w, mi, g, ln, n1, lw);
                     } else if (c_lpack) {
                         *reinterpret_cast<float4*>(&LW(w, mi)) = make_float4(w1, z1, n1, s_lin4[cur][lane].w);
                     } else {
@@ -1702,7 +1602,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
 // {V | G | 0} slots need 5).  One 12-B LDS-DMA (global_load_lds_dwordx3) and one 12-B store
 // per slot; otherwise the schedule of ffm_pipe_sg32_kernel.  Access-pattern ceiling of this
 // footprint: 182 M rows/s (profiles/ffm_r3/roofline_sg.log, mode 6), 16-B slots 138 M.
-// KEEP (round 6; default 2, variant 10 = 1, variant 9 = 0): the slot data kept in registers from
+// KEEP (round 6; default 2, the 64-bit-offset launch 0): the slot data kept in registers from
 // phase C, and with 2 the forward's image reads kept for the update, as in ffm_pipe_sg32_kernel
 // (the 16-B metadata reads of the b-side conflict where b wraps).
 template <int NS, typename OT, int KEEP = 0, int LT = 0>
@@ -1736,7 +1636,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     const OT bs = (OT)P.gstride * 4u;                    // block bytes per feature
     const int G = gridDim.x;
     char* vb = reinterpret_cast<char*>(Vt);
-    const bool latom = !LT && P.lin_atomic == 1 && G > 1;   // as in ffm_pipe_sg32_kernel
     if constexpr (LT != 0) {
         for (int t = tid; t < HD12_SIZE; t += 256) s_hd[t] = make_float2(0.f, 0.f);
     }
@@ -1917,7 +1816,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
             mi = m.x;
             mx = __int_as_float(m.z);
             lw = P.lpack ? s_lin4[cur][lane].x : s_lin[cur][0][lane];
-            if (latom) lw = lin_w(P, s_lin4[cur][lane]);
             if constexpr (LT != 0) {
                 if (P.hacc_on && mi >= 0 && kh >= 0) {
                     const float4 a = s_hacc[cur][lane];
@@ -2035,8 +1933,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
                 if (LT && hot) {
                     const float2 d = s_hd[kh];
                     s_hd[kh] = make_float2(d.x + (g - (sqrtf(n1) - sqrtf(ln)) / P.alpha * lw), d.y + g * g);
-                } else if (latom) {
-                    lin_add(P, w, mi, g, ln, n1, lw);
                 } else if (P.lpack) {
                     *reinterpret_cast<float4*>(&LW(w, mi)) = make_float4(w1, z1, n1, 0.f);
                 } else {
@@ -2080,42 +1976,57 @@ int default_blocks(int B, int grid, int cap = 256 * 8 * 4) {
     return grid > 0 ? grid : (B < cap ? B : cap);
 }
 
-// Per-element pipelined / lean dispatch (Kp == 4, packed, table < 4 GiB, F*F <= 2048); -1 when
-// the shape needs the generic kernel.
+// The tensors of one launch (hm_ffm_step's arguments), in the kernels' argument order.
+struct FFMArgs {
+    const int32_t *idx, *fld;
+    const float *val, *y;
+    void *V, *G;
+    float *w, *wz, *wn, *bias, *pred, *loss;
+};
+
+// The two kernel signatures: one table pointer (V and G share the slot, or G is found from the
+// layout), or V and G (ffm_row_kernel: void* G; ffm_pipe_sg32_kernel: float* G).
+using KernelV = void (*)(FFMParams, const int32_t*, const int32_t*, const float*, const float*, void*,
+                         float*, float*, float*, float*, float*, float*);
+template <typename GT>
+using KernelVG = void (*)(FFMParams, const int32_t*, const int32_t*, const float*, const float*, void*, GT*,
+                          float*, float*, float*, float*, float*, float*);
+
+void launch(KernelV k, int blocks, int tpb, size_t lds, hipStream_t stream, const FFMParams& P, const FFMArgs& a) {
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(tpb), lds, stream, P, a.idx, a.fld, a.val, a.y, a.V, a.w, a.wz, a.wn,
+                       a.bias, a.pred, a.loss);
+}
+template <typename GT>
+void launch(KernelVG<GT> k, int blocks, int tpb, size_t lds, hipStream_t stream, const FFMParams& P, const FFMArgs& a) {
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(tpb), lds, stream, P, a.idx, a.fld, a.val, a.y, a.V,
+                       reinterpret_cast<GT*>(a.G), a.w, a.wz, a.wn, a.bias, a.pred, a.loss);
+}
+
+// Slots per thread as a compile-time constant: f(std::integral_constant<int, NS>) with the first NS
+// of the ladder that covers `need` (the last one otherwise: the callers bound F).
+template <int N0, int... NR, typename Fn>
+void with_ns(int need, Fn&& f) {
+    if constexpr (sizeof...(NR) == 0) f(std::integral_constant<int, N0>{});
+    else if (need <= N0) f(std::integral_constant<int, N0>{});
+    else with_ns<NR...>(need, f);
+}
+
+// Per-element pipelined / lean dispatch (Kp == 4, packed, table < 4 GiB, F*F <= 2048): bf16 state
+// the LDS-DMA pipeline, fp32 the lean kernel; -1 when the shape needs the generic kernel.
 template <bool BF>
-int dispatch_lean(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-                  const float* y, void* VG, float* w, float* wz, float* wn, float* bias,
-                  float* pred, float* loss, int grid, int variant, hipStream_t stream) {
+int dispatch_lean(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t stream) {
     const size_t slot_b = BF ? 16 : 32;
     if (P.Kp != 4 || P.F > 45) return -1;
     if ((size_t)P.num_features * (size_t)P.fstride * slot_b >= ((size_t)1 << 32)) return -1;
-    const size_t meta = (size_t)P.F * 16 + 16 * 4;
-    const size_t sh = (size_t)P.F * P.F * (BF ? 8 : 16) + meta;
+    const size_t lean_lds = (size_t)P.F * P.F * 16 + (size_t)P.F * 16 + 16 * 4;   // image + meta
     const int need = (P.F * P.F + 255) / 256;
     const int blocks = default_blocks(P.B, grid);
     if (blocks <= 0) return 0;
-    // bf16: the LDS-DMA pipeline unless variant 2; fp32: the lean kernel unless variant 3
-    // (measured same-box, profiles/ffm_r2/fp32_pipe_ab.log: 52.5 M rows/s vs 51.2 M (+2.6 %),
-    // while the pipeline's extra row of staleness cost held-out logloss at 500 K rows: +0.019 vs
-    // sequential, lean +0.010)
-    if ((BF && variant != 2) || (!BF && variant == 3)) {
-#define HM_PIPE(NSV) hipLaunchKernelGGL((ffm_pipe_kernel<NSV, BF>), dim3(blocks), dim3(256), 0, stream, P, idx, \
-                                        fld, val, y, VG, w, wz, wn, bias, pred, loss)
-        if (need <= 2) { HM_PIPE(2); }
-        else if (need <= 4) { HM_PIPE(4); }
-        else if (need <= 6) { HM_PIPE(6); }
-        else { HM_PIPE(8); }
-#undef HM_PIPE
-        HM_LAUNCH_RET();
-    }
-#define HM_LEAN(NSV)                                                                                \
-    hipLaunchKernelGGL((ffm_lean_kernel<BF, NSV>), dim3(blocks), dim3(256), sh, stream, P, idx, fld, \
-                       val, y, VG, w, wz, wn, bias, pred, loss)
-    if (need <= 2) HM_LEAN(2);
-    else if (need <= 4) HM_LEAN(4);
-    else if (need <= 6) HM_LEAN(6);
-    else HM_LEAN(8);
-#undef HM_LEAN
+    with_ns<2, 4, 6, 8>(need, [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        if constexpr (BF) launch(ffm_pipe_kernel<NS>, blocks, 256, 0, stream, P, a);
+        else launch(ffm_lean_kernel<NS>, blocks, 256, lean_lds, stream, P, a);
+    });
     HM_LAUNCH_RET();
 }
 
@@ -2136,19 +2047,24 @@ __global__ __launch_bounds__(256) void ffm_hacc_kernel(FFMParams P, float* __res
     }
 }
 
-// lin_atomic: w <- f(z, n) for every feature record a row stepped (n > 0; a record never stepped
-// keeps its w, e.g. an imported model's).
-__global__ __launch_bounds__(256) void ffm_lin_derive_kernel(FFMParams P, float* __restrict__ w) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.num_features) return;
-    const float4 r = *reinterpret_cast<const float4*>(&LW(w, i));
-    if (r.z > 0.f) LW(w, i) = ftrl_weight(r.y, r.z, P.alpha, P.beta, P.lambda1, P.lambda2);
+// A training launch inside its side-table bracket (Q.hacc_on): records -> side table, train(), side
+// table -> records.  Without the side table: train() alone.
+template <typename Fn>
+int with_side_table(const FFMParams& Q, float* w, hipStream_t stream, Fn&& train) {
+    if (Q.hacc_on) {
+        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((Q.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
+        HM_LAUNCH_RET_IF_ERR();
+    }
+    train();
+    if (Q.hacc_on) {
+        HM_LAUNCH_RET_IF_ERR();
+        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((Q.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 1);
+    }
+    HM_LAUNCH_RET();
 }
 
-// Per-slot-G in 12-B bf16 slots {V | G}, 512-B feature blocks (Kp == 4, F <= 45, table < 4 GiB).
-int dispatch_sg12(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-                  const float* y, void* VG, float* w, float* wz, float* wn, float* bias,
-                  float* pred, float* loss, int grid, int variant, hipStream_t stream) {
+// Per-slot-G in 12-B bf16 slots {V | G}, 512-B feature blocks (Kp == 4, F <= 45).
+int dispatch_sg12(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t stream) {
     if (P.Kp != 4 || P.F > 45) return -1;
     // tables of 4 GiB and more (-feature_hashing >= 23 at 512-B blocks): 64-bit slot offsets
     const bool wide = (size_t)P.num_features * (size_t)P.gstride * 4 >= ((size_t)1 << 32);
@@ -2156,208 +2072,119 @@ int dispatch_sg12(const FFMParams& P, const int32_t* idx, const int32_t* fld, co
     int blocks = default_blocks(P.B, grid, 256 * 8 * 8);
     if (blocks <= 0) return 0;
     FFMParams Q = P;
-    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && P.nhot <= HD12_SIZE && blocks > 1 && !wide && variant != 9 && variant != 10;
+    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && P.nhot <= HD12_SIZE && blocks > 1 && !wide;
     if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID12);
-    if (Q.hacc_on) {
-        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
-        HM_LAUNCH_RET_IF_ERR();
-    }
-#define HM_P12(NSV) do { \
-        if (wide) hipLaunchKernelGGL((ffm_pipe_sg12_kernel<NSV, uint64_t>), dim3(blocks), dim3(256), 0, stream, \
-                                     P, idx, fld, val, y, VG, w, wz, wn, bias, pred, loss); \
-        else if (Q.hacc_on) hipLaunchKernelGGL((ffm_pipe_sg12_kernel<NSV, uint32_t, 2, 1>), dim3(blocks), dim3(256), 0, \
-                                               stream, Q, idx, fld, val, y, VG, w, wz, wn, bias, pred, loss); \
-        else if (variant == 9) hipLaunchKernelGGL((ffm_pipe_sg12_kernel<NSV, uint32_t>), dim3(blocks), dim3(256), 0, \
-                                                  stream, P, idx, fld, val, y, VG, w, wz, wn, bias, pred, loss); \
-        else if (variant == 10) hipLaunchKernelGGL((ffm_pipe_sg12_kernel<NSV, uint32_t, 1>), dim3(blocks), dim3(256), 0, \
-                                                   stream, P, idx, fld, val, y, VG, w, wz, wn, bias, pred, loss); \
-        else hipLaunchKernelGGL((ffm_pipe_sg12_kernel<NSV, uint32_t, 2>), dim3(blocks), dim3(256), 0, stream, \
-                                P, idx, fld, val, y, VG, w, wz, wn, bias, pred, loss); } while (0)
-    if (need <= 2) { HM_P12(2); }
-    else if (need <= 4) { HM_P12(4); }
-    else if (need <= 6) { HM_P12(6); }
-    else { HM_P12(8); }
-#undef HM_P12
-    if (Q.hacc_on) {
-        HM_LAUNCH_RET_IF_ERR();
-        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 1);
-    }
-    HM_LAUNCH_RET();
+    return with_side_table(Q, a.w, stream, [&] {
+        with_ns<2, 4, 6, 8>(need, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            if (wide) launch(ffm_pipe_sg12_kernel<NS, uint64_t>, blocks, 256, 0, stream, Q, a);
+            else if (Q.hacc_on) launch(ffm_pipe_sg12_kernel<NS, uint32_t, 2, 1>, blocks, 256, 0, stream, Q, a);
+            else launch(ffm_pipe_sg12_kernel<NS, uint32_t, 2>, blocks, 256, 0, stream, Q, a);
+        });
+    });
 }
 
-// Per-slot-G fp32 pipelined dispatch (Kp == 4 or 8, F <= 45, block layout, tables < 4 GiB): the
-// LDS-DMA ffm_pipe_sg32_kernel; -1 otherwise (bf16 V in this layout: the generic kernel; the
-// bf16 default is the 12-B slot layout of dispatch_sg12).
-int dispatch_sg32(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-                  const float* y, void* V, float* G, float* w, float* wz, float* wn, float* bias,
-                  float* pred, float* loss, int grid, int variant, hipStream_t stream) {
+// Per-slot-G fp32 pipelined dispatch (Kp == 4 or 8, F <= 45, block layout): the LDS-DMA
+// ffm_pipe_sg32_kernel; -1 otherwise (bf16 V in this layout: the generic kernel; the bf16 default
+// is the 12-B slot layout of dispatch_sg12).
+int dispatch_sg32(const FFMParams& P, const FFMArgs& a, int grid, int variant, hipStream_t stream) {
     if ((P.Kp != 4 && P.Kp != 8) || P.F > 45 || P.vpad <= 0) return -1;
     // tables of 4 GiB and more (-feature_hashing >= 23 at 896-B blocks): 64-bit slot offsets
     const bool wide = (size_t)P.num_features * (size_t)P.fstride * (size_t)(P.Kp * 4) >= ((size_t)1 << 32) ||
                       (size_t)P.num_features * (size_t)P.gstride * 4 >= ((size_t)1 << 32);
-    if (P.Kp == 8) {
-        // 32-B slots: 512-thread blocks, one per CU (107 KB of LDS at 39 fields)
-        if (variant == 8) return -1;
-        const int need = (P.F * P.F + 511) / 512;
-        int blocks = default_blocks(P.B, grid);
-        if (blocks <= 0) return 0;
-        // lin_atomic 4 as for k = 4 below (the 16 KB of block sums still leave one block per CU)
-        FFMParams Q = P;
-        Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && blocks > 1 && !wide && variant != 6 && variant != 9;
-        if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID);
-        if (Q.hacc_on) {
-            hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
-            HM_LAUNCH_RET_IF_ERR();
-        }
-#define HM_P32K8(NSV) do { \
-        if (wide) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint64_t, 512, 0, 2>), dim3(blocks), dim3(512), 0, stream, \
-                                     P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); \
-        else if (Q.hacc_on) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 512, 0, 2, 1, 1>), dim3(blocks), \
-                                               dim3(512), 0, stream, Q, idx, fld, val, y, V, G, w, wz, wn, \
-                                               bias, pred, loss); \
-        else if (variant == 6) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 512, 1, 2>), dim3(blocks), \
-                                                  dim3(512), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                                  bias, pred, loss); \
-        else if (variant == 9) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 512, 0, 2>), dim3(blocks), \
-                                                  dim3(512), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                                  bias, pred, loss); \
-        else hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 512, 0, 2, 1>), dim3(blocks), dim3(512), 0, stream, \
-                                P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); } while (0)
-        if (need <= 2) { HM_P32K8(2); }
-        else if (need <= 3) { HM_P32K8(3); }
-        else { HM_P32K8(4); }
-#undef HM_P32K8
-        if (Q.hacc_on) {
-            HM_LAUNCH_RET_IF_ERR();
-            hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 1);
-        }
-        HM_LAUNCH_RET();
-    }
-    const int need = (P.F * P.F + 255) / 256;
+    // k = 8, 32-B slots: 512-thread blocks, one per CU (107 KB of LDS at 39 fields)
+    const int tpb = P.Kp == 8 ? 512 : 256;
+    const int need = (P.F * P.F + tpb - 1) / tpb;
     int blocks = default_blocks(P.B, grid);
     if (blocks <= 0) return 0;
     // lin_atomic 4: the side table for a launch of more than one block (one block stores the
-    // records in row order: the sequential engine)
+    // records in row order: the sequential engine; at k = 8 its 16 KB of block sums still leave one
+    // block per CU).  It needs lin_defer: without the deferred wait, nlin == 0, phase F would read
+    // the DMA'd hot indices with no wait before it.
     FFMParams Q = P;
-    // (the side table needs lin_defer: without the deferred wait, nlin == 0, phase F would read
-    // the DMA'd hot indices with no wait before it)
-    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && blocks > 1 && !wide && variant != 6 && variant != 8 &&
-                variant != 9 && variant != 10;
+    Q.hacc_on = P.lin_atomic == 4 && P.lin_defer && blocks > 1 && !wide && variant != 6;
     if (Q.hacc_on && grid <= 0) blocks = default_blocks(P.B, grid, HACC_GRID);
-    if (Q.hacc_on) {
-        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 0);
-        HM_LAUNCH_RET_IF_ERR();
-    }
+    if (P.Kp == 8)
+        return with_side_table(Q, a.w, stream, [&] {
+            with_ns<2, 3, 4>(need, [&](auto ns) {
+                constexpr int NS = decltype(ns)::value;
+                if (wide) launch(ffm_pipe_sg32_kernel<NS, uint64_t, 512, 0, 2>, blocks, 512, 0, stream, Q, a);
+                else if (Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 512, 0, 2, 1, 1>, blocks, 512, 0, stream, Q, a);
+                else if (variant == 6) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 512, 1, 2>, blocks, 512, 0, stream, Q, a);
+                else launch(ffm_pipe_sg32_kernel<NS, uint32_t, 512, 0, 2, 1>, blocks, 512, 0, stream, Q, a);
+            });
+        });
     // The default kernel choice (variant 0) of a training launch of the default learner takes the
     // instantiation specialised for it (SG32_TRAIN above); anything else — predict, -w0, separate
-    // linear arrays, implicit fields or values, record atomics, wide tables, the A/B variants — the
-    // generic one.  Variant 11 = the same launch (LT, KEEP, grid) on the generic instantiation.
+    // linear arrays, implicit fields or values, wide tables, the all-atomic ramp — the generic one.
+    // Variant 11 = the same launch (LT, KEEP, grid) on the generic instantiation.
     const bool spec = variant == 0 && !wide && P.train && P.use_linear && P.lpack && P.lin_defer &&
-                      !P.use_bias && fld && val && P.lin_atomic != 1 &&
-                      (size_t)P.fstride * 16 == (size_t)P.gstride * 4;
-#define HM_P32(NSV) do { \
-        if (wide) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint64_t>), dim3(blocks), dim3(256), 0, stream, \
-                                     P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); \
-        else if (spec && Q.hacc_on) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2, 1, SG32_TRAIN>), \
-                                                  dim3(blocks), dim3(256), 0, stream, Q, idx, fld, val, y, V, G, w, wz, \
-                                                  wn, bias, pred, loss); \
-        else if (spec) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2, 0, SG32_TRAIN>), \
-                                          dim3(blocks), dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                          bias, pred, loss); \
-        else if (variant == 6) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 1>), dim3(blocks), \
-                                                  dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                                  bias, pred, loss); \
-        else if (variant == 8 && P.hot) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 2>), dim3(blocks), \
-                                                  dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                                  bias, pred, loss); \
-        else if (variant == 9) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t>), dim3(blocks), dim3(256), 0, \
-                                                  stream, P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); \
-        else if (variant == 10) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 1>), dim3(blocks), \
-                                                   dim3(256), 0, stream, P, idx, fld, val, y, V, G, w, wz, wn, \
-                                                   bias, pred, loss); \
-        else if (Q.hacc_on) hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2, 1>), dim3(blocks), \
-                                               dim3(256), 0, stream, Q, idx, fld, val, y, V, G, w, wz, wn, \
-                                               bias, pred, loss); \
-        else hipLaunchKernelGGL((ffm_pipe_sg32_kernel<NSV, uint32_t, 256, 0, 1, 2>), dim3(blocks), dim3(256), 0, stream, \
-                                P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss); } while (0)
-    if (need <= 2) { HM_P32(2); }
-    else if (need <= 4) { HM_P32(4); }
-    else if (need <= 6) { HM_P32(6); }
-    else { HM_P32(8); }
-#undef HM_P32
-    if (Q.hacc_on) {
-        HM_LAUNCH_RET_IF_ERR();
-        hipLaunchKernelGGL(ffm_hacc_kernel, dim3((P.nhot + 255) / 256), dim3(256), 0, stream, Q, w, 1);
-    }
-    HM_LAUNCH_RET();
+                      !P.use_bias && a.fld && a.val && (size_t)P.fstride * 16 == (size_t)P.gstride * 4;
+    return with_side_table(Q, a.w, stream, [&] {
+        with_ns<2, 4, 6, 8>(need, [&](auto ns) {
+            constexpr int NS = decltype(ns)::value;
+            if (wide) launch(ffm_pipe_sg32_kernel<NS, uint64_t>, blocks, 256, 0, stream, Q, a);
+            else if (spec && Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 1, SG32_TRAIN>, blocks, 256, 0, stream, Q, a);
+            else if (spec) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 0, SG32_TRAIN>, blocks, 256, 0, stream, Q, a);
+            else if (variant == 6) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 1>, blocks, 256, 0, stream, Q, a);
+            else if (Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 1>, blocks, 256, 0, stream, Q, a);
+            else launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2>, blocks, 256, 0, stream, Q, a);
+        });
+    });
 }
 
 template <int KC, bool BF, bool SG>
-int launch_ffm(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-               const float* y, void* V, void* G, float* w, float* wz, float* wn, float* bias,
-               float* pred, float* loss, int grid, hipStream_t stream) {
+int launch_ffm(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t stream) {
     const size_t meta = (size_t)6 * P.F * 4 + 16 * 4;
     const size_t stage = (size_t)P.F * P.F * KC * (BF ? 8 : 16);
-    const bool use_stage = stage + meta <= 64 * 1024;
     const int blocks = default_blocks(P.B, grid);
     if (blocks <= 0) return 0;
-    if (use_stage) {
-        hipLaunchKernelGGL((ffm_row_kernel<KC, true, BF, SG>), dim3(blocks), dim3(256), stage + meta, stream,
-                           P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss);
-    } else {
-        hipLaunchKernelGGL((ffm_row_kernel<KC, false, BF, SG>), dim3(blocks), dim3(256), meta, stream,
-                           P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss);
-    }
+    if (stage + meta <= 64 * 1024) launch(ffm_row_kernel<KC, true, BF, SG>, blocks, 256, stage + meta, stream, P, a);
+    else launch(ffm_row_kernel<KC, false, BF, SG>, blocks, 256, meta, stream, P, a);
     HM_LAUNCH_RET();
 }
 
 template <bool BF, bool SG>
-int launch_generic(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-                   const float* y, void* V, void* G, float* w, float* wz, float* wn, float* bias,
-                   float* pred, float* loss, int grid, hipStream_t stream) {
+int launch_generic(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t stream) {
     switch (P.Kp / 4) {
-        case 1: return launch_ffm<1, BF, SG>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
-        case 2: return launch_ffm<2, BF, SG>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
-        case 3: return launch_ffm<3, BF, SG>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
-        case 4: return launch_ffm<4, BF, SG>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
-        case 8: return launch_ffm<8, BF, SG>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
+        case 1: return launch_ffm<1, BF, SG>(P, a, grid, stream);
+        case 2: return launch_ffm<2, BF, SG>(P, a, grid, stream);
+        case 3: return launch_ffm<3, BF, SG>(P, a, grid, stream);
+        case 4: return launch_ffm<4, BF, SG>(P, a, grid, stream);
+        case 8: return launch_ffm<8, BF, SG>(P, a, grid, stream);
         default: return (int)hipErrorInvalidValue;
     }
 }
 
 // *fast = 1 when a pipelined / lean kernel ran (it defers multi-hot rows when P.defer is set).
 template <bool BF>
-int dispatch(const FFMParams& P, const int32_t* idx, const int32_t* fld, const float* val,
-             const float* y, void* V, void* G, float* w, float* wz, float* wn, float* bias,
-             float* pred, float* loss, int grid, int packed, int slot_g, int variant, hipStream_t stream,
-             int* fast) {
+int dispatch(const FFMParams& P, const FFMArgs& a, int grid, int packed, int slot_g, int variant,
+             hipStream_t stream, int* fast) {
     *fast = 1;
     if (slot_g) {
         if (P.gfstride == 3) {
-            // 12-B {V | G} slots: the pipelined kernel; rows wider than 45 features or tables of
-            // 4 GiB and more (32-bit offsets there) take the generic kernel with 64-bit offsets
-            // (slot stride 6 bf16, feature stride = the block)
+            // 12-B {V | G} slots: the pipelined kernel; rows wider than 45 features take the
+            // generic kernel with 64-bit offsets (slot stride 6 bf16, feature stride = the block)
             if (!BF) return (int)hipErrorInvalidValue;
-            const int rc = variant == 1 ? -1 : dispatch_sg12(P, idx, fld, val, y, V, w, wz, wn, bias, pred, loss, grid, variant, stream);
+            const int rc = variant == 1 ? -1 : dispatch_sg12(P, a, grid, stream);
             if (rc != -1) return rc;
             *fast = 0;
-            return launch_generic<true, true>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
+            return launch_generic<true, true>(P, a, grid, stream);
         }
         if (variant != 1 && !BF && P.gfstride == 1) {
-            const int rc = dispatch_sg32(P, idx, fld, val, y, V, reinterpret_cast<float*>(G), w, wz, wn,
-                                         bias, pred, loss, grid, variant, stream);
+            const int rc = dispatch_sg32(P, a, grid, variant, stream);
             if (rc != -1) return rc;
         }
         *fast = 0;
-        return launch_generic<BF, true>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
+        return launch_generic<BF, true>(P, a, grid, stream);
     }
     if (packed && variant != 1) {
-        const int rc = dispatch_lean<BF>(P, idx, fld, val, y, V, w, wz, wn, bias, pred, loss, grid, variant, stream);
+        const int rc = dispatch_lean<BF>(P, a, grid, stream);
         if (rc != -1) return rc;
         // other shapes: the generic kernel handles the packed strides too (G = V + Kp)
     }
     *fast = 0;
-    return launch_generic<BF, false>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
+    return launch_generic<BF, false>(P, a, grid, stream);
 }
 
 // The deferred multi-hot rows of a pipelined launch: ffm_row_kernel over the list (grid of
@@ -2365,16 +2192,13 @@ int dispatch(const FFMParams& P, const int32_t* idx, const int32_t* fld, const f
 constexpr int DEFER_BLOCKS = 512;
 
 template <bool BF>
-int launch_deferred(FFMParams P, const int32_t* idx, const int32_t* fld, const float* val,
-                    const float* y, void* V, void* G, float* w, float* wz, float* wn, float* bias,
-                    float* pred, float* loss, int slot_g, int grid_req, hipStream_t stream) {
+int launch_deferred(FFMParams P, const FFMArgs& a, int slot_g, int grid_req, hipStream_t stream) {
     P.list_mode = 1;
     // an explicit grid bounds the deferred rows' concurrency too (grid = 1: one block trains
     // them in list order, after the batch's other rows)
     const int cap = grid_req > 0 && grid_req < DEFER_BLOCKS ? grid_req : DEFER_BLOCKS;
     const int grid = P.B < cap ? P.B : cap;
-    return slot_g ? launch_generic<BF, true>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream)
-                  : launch_generic<BF, false>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, stream);
+    return slot_g ? launch_generic<BF, true>(P, a, grid, stream) : launch_generic<BF, false>(P, a, grid, stream);
 }
 
 }  // namespace
@@ -2383,10 +2207,11 @@ int launch_deferred(FFMParams P, const int32_t* idx, const int32_t* fld, const f
 // ip layout (ints)  : B, F, num_features, num_fields, Kp, classification, train, use_linear,
 //                     use_bias, norm, grid, reload, bf16_state, seed, packed, variant, fstride,
 //                     slot_g, gstride, vpad, tail16, gfstride, lin_defer, bias_every, lstride, lpack,
-//                     lin_atomic
+//                     lin_atomic, nhot
 // lstride = floats between consecutive features' w / wz / wn (1: separate arrays; the records of
 //           ops/ffm.py lin_record_views: the feature block's size); lpack = 1: {w, z, n} are one
 //           16-B record (wz = w + 1, wn = w + 2), DMA'd and stored as one 16-B access
+// lin_atomic = 0: plain record stores; 4: the side table of the nhot hot features (FFMParams)
 // slot_g = 1: one fp32 AdaGrad accumulator per (feature, field) slot, G[i * gstride + f * gfstride];
 //             bf16 V in 12-B slots {V | G} (G = V + 8 B, gfstride 3): ffm_pipe_sg12_kernel; fp32 V
 //             in the block layout (G = V + vpad * Kp * 4 B, vpad > 0): ffm_pipe_sg32_kernel (Kp 4:
@@ -2396,14 +2221,23 @@ int launch_deferred(FFMParams P, const int32_t* idx, const int32_t* fld, const f
 // slot_g = 0 (per-element G shaped like V): packed = 1: V and G are the two halves of one
 //             [num_features][fstride][2][Kp] table (G == V + Kp elements, slot stride 2*Kp); 0:
 //             separate [.][.][Kp] tables.
-// variant (A/B): 0 = auto (per-slot: the sg12 / sg32 pipelines; per-element bf16:
-// ffm_pipe_kernel, fp32: ffm_lean_kernel), 1 = the generic ffm_row_kernel, 2 = ffm_lean_kernel
-// for bf16, 3 = ffm_pipe_kernel for fp32 (per-element G), 6 = ffm_pipe_sg32_kernel with every
-// slot update added by float atomics (no lost update; the learner's early-training ramp,
-// models/ffm.py RAMP_*; G-only atomics were measured as variant 7 and removed: the full gap at
-// 12 M rows/s, profiles/r4/ffm_g_atomic_bench_ab.log); 11 = the default sg32 kernel choice (same
-// LT, KEEP and grid) forced onto the generic instantiation, CFG = 0, where the default takes the
-// one specialised for a training launch (SG32_TRAIN; round 7, k <= 4 only).  Measured and removed: 512-thread sg32
+// variant: 0 = auto (per-slot: the sg12 / sg32 pipelines; per-element bf16: ffm_pipe_kernel, fp32:
+// ffm_lean_kernel), 1 = the generic ffm_row_kernel, 6 = ffm_pipe_sg32_kernel with every slot update
+// added by float atomics (no lost update; the learner's early-training ramp, models/ffm.py
+// RAMP_*), 11 = the default sg32 kernel choice (same LT, KEEP and grid) forced onto the generic
+// instantiation, CFG = 0, where the default takes the one specialised for a training launch
+// (SG32_TRAIN; round 7, k <= 4 only).  Any other value is an error.  Measured and removed:
+//   2, ffm_lean_kernel on bf16 state: 88 vs 101 M rows/s (profiles/ffm_r2/ab_pipe_v1.log ...);
+//   3, ffm_pipe_kernel on fp32 state: 52.5 vs 51.2 M rows/s, held-out +0.019 vs +0.010 at 500 K rows
+//      (profiles/ffm_r2/fp32_pipe_ab.log);
+//   7, G-only atomics: the full gap at 12 M rows/s (profiles/r4/ffm_g_atomic_bench_ab.log);
+//   8, atomics on the slots of per-feature-flagged hot features: 4.7-6.2 vs 74.4 M rows/s
+//      (profiles/r5/ffm_hot_probe.jsonl);
+//   9 / 10, KEEP = 0 / 1 on the default launches: 89.2-89.4 / 92.8-95.4 vs 94.2-97.6 M rows/s fp32
+//      (profiles/r6/keep/bench_keep_ab.log, bench_keep2_ab.log);
+//   lin_atomic 1 - 3, float atomics on the linear records (all / flagged / unflagged features):
+//      8.7 / 8.7 / 82.6 M rows/s, the last at an unchanged gap (profiles/r6/linhot/).
+// Also measured and removed: 512-thread sg32
 // blocks (75.7-76.1 vs 75.6 M rows/s, profiles/r4/ffm_512_thread_ab.log); a paired-slot sg32
 // kernel holding each (a, b) / (b, a) slot pair in one thread's registers instead of a transposed
 // LDS image (4 rows in flight per CU instead of 2): 58.1-58.4 vs 74.9-75.5 M rows/s — the (b, a)
@@ -2415,11 +2249,11 @@ int launch_deferred(FFMParams P, const int32_t* idx, const int32_t* fld, const f
 // per CU does not move this kernel.  Round 5 re-tried it after the linear records (53.4 KB of LDS
 // with the 4-B linear zone aliased onto the 16-B one, forced to 3 waves per SIMD): 168 VGPRs with
 // 21 spilled, 63.2 vs 89.6 M rows/s (profiles/r5/bench_rg_ab.log).
-// aux (host array of 4 pointer-sized entries, or null): aux[0] = per-feature hot flags (variant 8)
-// or null; aux[1] = the multi-hot deferral buffer int32 [1 + B] or null (then a multi-hot row is
+// aux (host array of 7 pointer-sized entries, or null): aux[0] = reserved, null;
+// aux[1] = the multi-hot deferral buffer int32 [1 + B] or null (then a multi-hot row is
 // updated slot by slot by the pipelined kernels: racing stores of one address, one wins);
 // aux[2] = the global-bias shards fp32 [S][32] (training with -w0) or null; aux[3] = S, the
-// shard count (1 .. 64), as an integer.
+// shard count (1 .. 64), as an integer; aux[4..6] = lin_atomic 4: hidx, hot_id, hacc (FFMParams).
 // Measured and removed in round 5 (docs/perf_notes.md "where the fp32 same-stream gap comes
 // from"): reload-delta stores, SC1 DMA loads, write-through (device-scope) stores, agent / system
 // acquires, a coherent re-read, 512-thread and one-block-per-CU launches, one table replica per
@@ -2428,8 +2262,9 @@ HM_API int hm_ffm_step(const int32_t* ip, const float* hp, const int32_t* idx, c
                        const float* val, const float* y, void* V, void* G, float* w, float* wz,
                        float* wn, float* bias, float* pred, float* loss, void* const* aux,
                        hipStream_t stream) {
+    const FFMArgs a{idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss};
     FFMParams P;
-    P.hot = aux ? reinterpret_cast<const uint8_t*>(aux[0]) : nullptr;
+    P.reserved = nullptr;
     P.defer = aux ? reinterpret_cast<int32_t*>(aux[1]) : nullptr;
     P.list_mode = 0;
     P.B = ip[0]; P.F = ip[1]; P.num_features = ip[2]; P.num_fields = ip[3]; P.Kp = ip[4];
@@ -2441,6 +2276,8 @@ HM_API int hm_ffm_step(const int32_t* ip, const float* hp, const int32_t* idx, c
     P.seed = (uint32_t)ip[13];
     const int packed = ip[14];
     const int variant = ip[15];
+    if (variant != 0 && variant != 1 && variant != 6 && variant != 11) return (int)hipErrorInvalidValue;
+    if (ip[26] != 0 && ip[26] != 4) return (int)hipErrorInvalidValue;
     P.sstride = packed ? 2 * P.Kp : P.Kp;
     P.fstride = ip[16] > 0 ? ip[16] : P.num_fields;
     const int slot_g = ip[17];
@@ -2507,17 +2344,8 @@ HM_API int hm_ffm_step(const int32_t* ip, const float* hp, const int32_t* idx, c
         if (e != hipSuccess) return (int)e;
     }
     int fast = 0;
-    const int rc = bf16 ? dispatch<true>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, packed, slot_g, variant, stream, &fast)
-                        : dispatch<false>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, grid, packed, slot_g, variant, stream, &fast);
-    if (rc != 0) return rc;
-    if (fast && P.train && P.use_linear && P.lin_atomic == 1) {
-        // the stored w of every record a row stepped: w = f(z, n) (before the deferred rows, whose
-        // generic kernel reads w)
-        hipLaunchKernelGGL(ffm_lin_derive_kernel, dim3((P.num_features + 255) / 256), dim3(256), 0, stream, P, w);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    if (!fast || !P.defer) return rc;
-    return bf16 ? launch_deferred<true>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, slot_g, grid, stream)
-                : launch_deferred<false>(P, idx, fld, val, y, V, G, w, wz, wn, bias, pred, loss, slot_g, grid, stream);
+    const int rc = bf16 ? dispatch<true>(P, a, grid, packed, slot_g, variant, stream, &fast)
+                        : dispatch<false>(P, a, grid, packed, slot_g, variant, stream, &fast);
+    if (rc != 0 || !fast || !P.defer) return rc;
+    return bf16 ? launch_deferred<true>(P, a, slot_g, grid, stream) : launch_deferred<false>(P, a, slot_g, grid, stream);
 }

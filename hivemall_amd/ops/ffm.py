@@ -41,10 +41,9 @@ class FFMHyper:
 
 
 _CALLS = 0  # per-launch counter mixed into the stochastic-rounding seed
-# kernel variant (A/B only; csrc/kernels/ffm.hip hm_ffm_step): 0 = auto (per-slot G: the
-# sg12 / sg32 LDS-DMA pipelines; per-element G, K <= 4 packed: bf16 ffm_pipe_kernel, fp32
-# ffm_lean_kernel), 1 = the generic ffm_row_kernel, 2 = ffm_lean_kernel for bf16,
-# 3 = ffm_pipe_kernel for fp32
+# kernel variant: 0 = auto, 1 = the generic ffm_row_kernel, 6 = all-atomic slot updates (the learner's
+# ramp), 11 = the default launch on the generic sg32 instantiation (hm_ffm_step lists the retired ones)
+VARIANTS = (0, 1, 6, 11)
 _VARIANT = int(os.environ.get("HM_FFM_VARIANT", "0"))
 
 
@@ -225,11 +224,12 @@ _LIN_DEFER = int(os.environ.get("HM_FFM_LIN_DEFER", "1") != "0")
 #     (z, n) in a dense side table during a launch; each block sums its rows' steps of them in LDS
 #     and adds the sums by float atomics when it ends; the other features keep plain record stores
 #     (csrc/kernels/ffm.hip ffm_hacc_kernel).
-#   1: every row's (z, n) steps by float atomics on the records (A/B: 8.7 M rows/s — the atomics
-#     drop the hot features' block lines from L2)
 #   0: plain record stores (a concurrent row's step to the same feature is lost)
+# Measured and removed: 1 - 3, float atomics on the records themselves (8.7 M rows/s — the atomics
+# drop the hot features' block lines from L2; profiles/r6/linhot/).
 # The host model benchmarks/ffm_hogwild_sim.py puts ~80 % of the same-stream gap on lost linear
 # steps (docs/perf_notes.md, round 6).
+LIN_MODES = (0, 4)
 _LIN_ATOMIC = int(os.environ.get("HM_FFM_LIN_ATOMIC", "4"))
 _LIN_HOT_N = min(int(os.environ.get("HM_FFM_LIN_HOT", "2048")), 2048)   # <= HD_SIZE of the kernel
 _LIN_HOT: dict = {}   # (device, w.data_ptr(), NF, H) -> (hidx int32 [NF], hot_id int32 [H], hacc f32 [H, 32], [launches])
@@ -299,16 +299,21 @@ def _has_multihot(idx: torch.Tensor, fld: torch.Tensor | None) -> bool:
 def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torch.Tensor | None,
              y: torch.Tensor | None, hyper: FFMHyper, train: bool = True,
              pred: torch.Tensor | None = None, loss: torch.Tensor | None = None,
-             grid: int = 0, variant: int | None = None, hot: torch.Tensor | None = None,
-             lin_mode: int | None = None) -> None:
-    """One fused pass over a padded-ELL batch.  ``lin_mode``: the linear steps' form
-    (HM_FFM_LIN_ATOMIC values; None = the module default, the side table).
+             grid: int = 0, variant: int | None = None, lin_mode: int | None = None) -> None:
+    """One fused pass over a padded-ELL batch.  ``variant`` / ``lin_mode``: the kernel choice / the
+    linear steps' form (VARIANTS / LIN_MODES, else a ValueError; None = the module defaults above).
 
     state: dict with V, G ([NF, NFLD, Kp] f32 or bf16; either two contiguous tables or the two
     halves of one packed [NF, NFLD, 2, Kp] table, see :func:`is_packed`), w, wz, wn ([NF] f32),
     bias ([4] f32).
     idx/fld int32 [B, F]; val f32 [B, F]; y f32 [B] in {-1,+1} (classification) or real.
     """
+    auto = variant is None and _VARIANT == 0
+    variant = _VARIANT if variant is None else int(variant)
+    lin_mode = _LIN_ATOMIC if lin_mode is None else int(lin_mode)
+    for what, v, live in (("kernel variant", variant, VARIANTS), ("linear mode", lin_mode, LIN_MODES)):
+        if v not in live:   # a retired number used to run the default silently
+            raise ValueError(f"FFM {what} {v}: the live values are {live}")
     V = state["V"]
     B, F = idx.shape
     NF, NFLD, Kp = V.shape
@@ -326,7 +331,7 @@ def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torc
         assert pred.shape[0] >= B
     if loss is not None:
         assert loss.shape[0] >= B
-    if V.is_cuda and train and int(grid) == 1 and variant is None and _VARIANT == 0 and _has_multihot(idx, fld):
+    if V.is_cuda and train and int(grid) == 1 and auto and _has_multihot(idx, fld):
         # one block is documented as the sequential learner: a multi-hot row would be deferred by
         # the pipelined kernels until after the batch's other rows, so the whole launch
         # goes to the generic kernel, which trains every row in order with grouped updates
@@ -369,21 +374,15 @@ def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torc
     ip = np.array([B, F, NF, NFLD, Kp, int(hyper.classification), int(train), int(hyper.use_linear),
                    int(hyper.use_bias), int(hyper.norm), int(grid),
                    int((not packed) if hyper.reload is None else hyper.reload), int(bf16),
-                   (hyper.seed * 1000003 + _CALLS) & 0x7FFFFFFF, int(packed),
-                   _VARIANT if variant is None else int(variant),
+                   (hyper.seed * 1000003 + _CALLS) & 0x7FFFFFFF, int(packed), variant,
                    field_stride(V), int(slot_g), gstride, block[0], block[1],
                    G.stride(1) if slot_g else 0, _LIN_DEFER, BIAS_EVERY] + list(_lin_addressing(state))
-                  + [_LIN_ATOMIC, 0],
-                  dtype=np.int32)
+                  + [lin_mode, 0], dtype=np.int32)
     hp = hyper.hp()
     p = _native.ptr
     args = (ip.ctypes.data, hp.ctypes.data, p(idx), p(fld), p(val), p(y), p(V), p(G),
             p(state["w"]), p(state["wz"]), p(state["wn"]), p(state["bias"]), p(pred), p(loss))
     if V.is_cuda:
-        if hot is not None:
-            assert hot.dtype == torch.uint8 and hot.numel() >= NF and hot.device == V.device
-        # multi-hot rows (a repeated field or feature) are deferred by the pipelined kernels to
-        # the grouped-update kernel through this buffer (same stream, no host sync)
         bsh = _bias_shards(V.device) if (train and hyper.use_bias and BIAS_SHARDS > 0) else None
         if bsh is not None:
             # shard 0 <- the bias FTRL state (z0, n0), the other shards 0; the pipelined kernels add
@@ -392,15 +391,15 @@ def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torc
             zn0 = b[1:3].clone()
             bsh.zero_()
             bsh[0, :2] = zn0
-        lin_mode, hidx, hot_id, hacc = _LIN_ATOMIC if lin_mode is None else int(lin_mode), None, None, None
-        if lin_mode == 4:
-            if train and hyper.use_linear and _lin_addressing(state)[1]:
-                # the bf16 kernel's LDS holds the sums of 1,024 hot features (HD12_SIZE)
-                hidx, hot_id, hacc = _lin_hot_tables(state, idx, 1024 if bf16 else _LIN_HOT_N)
-            if hot_id is None or hot_id.numel() == 0:
-                lin_mode, hidx, hot_id, hacc = 0, None, None, None
-        ip[26], ip[27] = lin_mode, hot_id.numel() if hot_id is not None else 0
-        aux = (ctypes.c_void_p * 7)(p(hot), p(_defer_buffer(V.device, B)) if (train and _DEFER_ON) else None,
+        hidx = hot_id = hacc = None
+        if lin_mode == 4 and train and hyper.use_linear and _lin_addressing(state)[1]:
+            # the bf16 kernel's LDS holds the sums of 1,024 hot features (HD12_SIZE)
+            hidx, hot_id, hacc = _lin_hot_tables(state, idx, 1024 if bf16 else _LIN_HOT_N)
+        nhot = hot_id.numel() if hot_id is not None else 0
+        ip[26], ip[27] = lin_mode if nhot else 0, nhot     # no hot feature: plain record stores
+        # aux[0] is reserved.  aux[1]: multi-hot rows (a repeated field or feature) are deferred by the
+        # pipelined kernels to the grouped-update kernel through this buffer (same stream, no host sync)
+        aux = (ctypes.c_void_p * 7)(None, p(_defer_buffer(V.device, B)) if (train and _DEFER_ON) else None,
                                     p(bsh), bsh.shape[0] if bsh is not None else 0,
                                     p(hidx), p(hot_id), p(hacc))
         rc = _native.hip().hm_ffm_step(*args, ctypes.addressof(aux), _native.stream_of(V.device))

@@ -653,3 +653,32 @@ def test_ffm_engine_options_grid_and_atomic_rows():
         assert (t.grid, t.atomic_rows) == (0, 12345)
     finally:
         ffm_model.RAMP_ROWS = old
+
+
+def test_ffm_step_rejects_retired_variants_and_linear_modes(monkeypatch):
+    """A retired or never-assigned kernel variant / linear mode is a ValueError on any device (it
+    used to run the default silently), whether it comes from the argument or from the environment's
+    module default; the live values run."""
+    from hivemall_amd.ops import ffm as ffm_ops
+
+    t = _trainer("cpu", nf=8, nfld=3)
+    idx = torch.tensor([[0, 3, 6], [1, 4, 7]], dtype=torch.int32)
+    y = torch.tensor([1.0, -1.0])
+    for v in (2, 3, 8, 9, 10, 7):
+        with pytest.raises(ValueError, match="0, 1, 6, 11"):
+            ffm_step(t.state, idx, None, None, y, t.hyper, variant=v)
+        monkeypatch.setattr(ffm_ops, "_VARIANT", v)
+        with pytest.raises(ValueError, match="0, 1, 6, 11"):
+            ffm_step(t.state, idx, None, None, y, t.hyper)
+        monkeypatch.setattr(ffm_ops, "_VARIANT", 0)
+    for m in (1, 2, 3):
+        with pytest.raises(ValueError, match="0, 4"):
+            ffm_step(t.state, idx, None, None, y, t.hyper, lin_mode=m)
+        monkeypatch.setattr(ffm_ops, "_LIN_ATOMIC", m)
+        with pytest.raises(ValueError, match="0, 4"):
+            ffm_step(t.state, idx, None, None, y, t.hyper)
+        monkeypatch.setattr(ffm_ops, "_LIN_ATOMIC", 4)
+    for v in (0, 1, 6, 11):
+        ffm_step(t.state, idx, None, None, y, t.hyper, variant=v)
+    for m in (0, 4):
+        ffm_step(t.state, idx, None, None, y, t.hyper, lin_mode=m)
