@@ -48,6 +48,28 @@ __device__ __forceinline__ float wave_sum_uniform(float v) {
     v += dpp_take<0x143, 0xC>(v);    // row_bcast:31 into rows 2, 3
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
+// The same in fp64: every permute moves the two halves of the value (12 v_mov_b32_dpp and
+// 6 v_add_f64 against the 12 ds_bpermute_b32 of wave_sum(double)), the total is read from lane 63
+// into scalar registers.
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ double dpp_take(double v) {
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROW_MASK, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xF, false);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_sum_uniform(double v) {
+    v += dpp_take<0xB1>(v);          // quad_perm [1,0,3,2]
+    v += dpp_take<0x4E>(v);          // quad_perm [2,3,0,1]
+    v += dpp_take<0x141>(v);         // row_half_mirror
+    v += dpp_take<0x140>(v);         // row_mirror
+    v += dpp_take<0x142, 0xA>(v);    // row_bcast:15 into rows 1, 3
+    v += dpp_take<0x143, 0xC>(v);    // row_bcast:31 into rows 2, 3
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, 63);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), 63);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

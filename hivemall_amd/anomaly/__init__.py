@@ -13,7 +13,7 @@ import math
 import numpy as np
 
 from ..registry import udf
-from ..utils.options import Options, flag, opt
+from ..utils.options import Options, UDFArgumentException, flag, opt
 
 _CF_OPTS = Options([
     opt("k", None, 7, int, "Order of the AR model"),
@@ -135,14 +135,34 @@ _SST_OPTS = Options([
     opt("r", "n_component", 3, int, "Rank of the past subspace"),
     opt("k", "n_dim", 5, int, "Rank of the current subspace"),
     opt("th", "threshold", -1.0, float, "Change-point threshold"),
+    opt("engine", None, "auto", str, "auto | native | numpy: native = the batched Jacobi SVD "
+        "engine (ops/sst.py); auto = native on a cuda session for a shape inside its limits, "
+        "numpy otherwise"),
     flag("ika", None, "Use the implicit Krylov approximation",
          inert="SST uses an exact (batched) SVD")], "sst")
 
 
+def _sst_native(x: np.ndarray, w, n, m, g, r, k, th, device):
+    """The rows of ``sst`` from ``ops.sst.sst_scores`` on ``device``."""
+    import torch
+
+    from ..ops import sst as ops_sst
+
+    try:
+        score = ops_sst.sst_scores(torch.from_numpy(x).to(device), w, n, m, g, r, k)
+    except ValueError as ex:
+        raise UDFArgumentException(str(ex)) from None
+    score = score.cpu().tolist()
+    return [[v] for v in score] if th < 0 else [[v, v > th] for v in score]
+
+
 @udf("sst", vectorized=True)
-def sst(xs, options=None):
+def sst(xs, options=None, session=None):
     """Singular spectrum transformation score per point: 1 - (largest singular value of
-    U_pastᵀ U_current)² between the top-r past and top-k current subspaces."""
+    U_pastᵀ U_current)² between the top-r past and top-k current subspaces. `-engine native`
+    runs the batched Jacobi SVD engine (ops/sst.py: the gfx950 kernel on a cuda device, its
+    OpenMP twin on the CPU); `-engine auto` (default) picks it on a cuda session when the shape is
+    inside its limits (w, n, m <= 64) and the per-point LAPACK loop otherwise."""
     o = options[0] if isinstance(options, (list, tuple, np.ndarray)) else options
     c = _SST_OPTS.parse(o)
     w = c["w"]
@@ -150,7 +170,22 @@ def sst(xs, options=None):
     m = c["m"] or w
     g = c["g"] if c["g"] is not None else -w
     r, k = c["r"], c["k"]
+    engine = c["engine"]
+    if engine not in ("auto", "native", "numpy"):
+        raise UDFArgumentException(f"sst: -engine must be auto, native or numpy, got {engine!r}")
     x = np.asarray(list(xs), dtype=np.float64)
+    if engine != "numpy":
+        from ..models.base import resolve_device
+        from ..ops.sst import supports
+
+        dev = None if session is None or session.device is None else resolve_device(session.device)
+        if engine == "native":
+            return _sst_native(x, w, n, m, g, r, k, c["th"], dev or resolve_device(None))
+        # auto: the native engine on a cuda session, for a shape inside its limits and finite
+        # samples; everything else runs below as it always did
+        if (dev is not None and dev.type == "cuda" and supports(w, n, m, g, r, k)
+                and bool(np.isfinite(x).all())):
+            return _sst_native(x, w, n, m, g, r, k, c["th"], dev)
     out = []
     need = w + n + max(0, -g) + m
     for t in range(len(x)):
@@ -166,3 +201,6 @@ def sst(xs, options=None):
         score = float(1.0 - (s[0] ** 2 if s.size else 0.0))
         out.append([score] if c["th"] < 0 else [score, score > c["th"]])
     return out
+
+
+sst.wants_session = True

@@ -38,7 +38,8 @@ def _call(fd, df: pd.DataFrame, args, device=None):
     n = len(df)
     if fd.kind == registry.UDF:
         if fd.vectorized:
-            res = fd.impl(*cols)
+            kw = {"session": _DeviceSession(device)} if getattr(fd.impl, "wants_session", False) else {}
+            res = fd.impl(*cols, **kw)
             return pd.Series(list(res) if not isinstance(res, pd.Series) else res, index=df.index)
         lists = [c.tolist() if isinstance(c, pd.Series) else None for c in cols]
         vals = [fd.impl(*[l[i] if l is not None else c for l, c in zip(lists, cols)]) for i in range(n)]

@@ -1514,7 +1514,8 @@ class Session:
         args = [self.eval(a, fr, ctes, vals) for a in f.args]
         if fd is not None and fd.kind == registry.UDF:
             if fd.vectorized:
-                res = fd.impl(*[_ser(a, n) if isinstance(a, pd.Series) else a for a in args])
+                kwargs = {"session": self} if getattr(fd.impl, "wants_session", False) else {}
+                res = fd.impl(*[_ser(a, n) if isinstance(a, pd.Series) else a for a in args], **kwargs)
                 return _ser(res if not isinstance(res, list) else pd.Series(res, dtype=object), n)
             cols = [_ser(a, n).tolist() if isinstance(a, pd.Series) else None for a in args]
             out = []
