@@ -41,6 +41,13 @@ def _call(fd, df: pd.DataFrame, args, device=None):
             kw = {"session": _DeviceSession(device)} if getattr(fd.impl, "wants_session", False) else {}
             res = fd.impl(*cols, **kw)
             return pd.Series(list(res) if not isinstance(res, pd.Series) else res, index=df.index)
+        batch = getattr(fd.impl, "batch", None)
+        if batch is not None:
+            # column-at-once form of a per-row UDF (minhashes, bbit_minhash); None -> per row.
+            # The DSL calls the function for NULL rows too, hence null_first=False.
+            res = batch(*cols, session=_DeviceSession(device), null_first=False)
+            if res is not None:
+                return pd.Series(res.tolist(), index=df.index, dtype=object).infer_objects()
         lists = [c.tolist() if isinstance(c, pd.Series) else None for c in cols]
         vals = [fd.impl(*[l[i] if l is not None else c for l, c in zip(lists, cols)]) for i in range(n)]
         return pd.Series(vals, index=df.index, dtype=object).infer_objects()
@@ -50,6 +57,15 @@ def _call(fd, df: pd.DataFrame, args, device=None):
     # UDTF
     lists = [c.tolist() if isinstance(c, pd.Series) else [c] * n for c in cols]
     if fd.per_row:
+        batch = getattr(fd.impl, "batch", None)
+        if batch is not None and getattr(fd.impl, "batch_select", False):
+            kw = {"session": _DeviceSession(device)} if getattr(batch, "wants_session", False) else {}
+            res = batch(*lists, **kw)
+            if res is not None:
+                df_out = pd.DataFrame({i: c for i, c in enumerate(res[1])})
+                if fd.cols and len(fd.cols) == df_out.shape[1]:
+                    df_out.columns = list(fd.cols)
+                return df_out
         rows = []
         for i in range(n):
             rows.extend(tuple(t) for t in fd.impl(*[l[i] for l in lists]))

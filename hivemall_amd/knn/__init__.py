@@ -232,6 +232,185 @@ def bbit_minhash(features, num_hashes: int = 128, b: int = 1):
     return format(bits, "x")
 
 
+# The column-at-once forms: one pass of ops/minhash.py (the gfx950 kernel, or its OpenMP twin on the
+# CPU) over the whole packed column instead of num_hashes * len(row) ctypes calls per row.  The
+# results equal the per-row functions above, row for row; a column the engine does not take
+# (pack_feature_column -> None) goes through them.
+def _engine_range(num_hashes: int, key_groups: int = 1) -> bool:
+    from ..ops.minhash import H_MAX
+
+    return num_hashes >= 1 and key_groups >= 1 and num_hashes * key_groups <= H_MAX
+
+
+def _column_signatures(col, num_hashes: int, device=None):
+    """int32 [n_rows, num_hashes] on ``device``, or None when the column cannot be packed."""
+    from ..models.base import resolve_device
+    from ..ops import minhash as mh
+
+    packed = mh.pack_feature_column(col)
+    if packed is None:
+        return None
+    dev = resolve_device(device)
+    return mh.minhash_signatures(*(t.to(dev) for t in packed), num_hashes, check=False)   # packed here
+
+
+def minhash_signatures(col, num_hashes: int, device=None) -> torch.Tensor:
+    """int32 [n_rows, num_hashes] (uint32 bit patterns): per row of the feature column, the
+    unsigned minimum over its feature names of MurmurHash3_x86_32 under the seeds
+    ``0..num_hashes-1``; 0 for an empty or NULL row.  ``col`` is a sequence / Series of lists of
+    ``"name[:value]"`` strings or an Arrow list<string>.  Runs on ``device`` (default: the GPU
+    when there is one)."""
+    sig = _column_signatures(col, num_hashes, device)
+    if sig is None:
+        raise ValueError("minhash_signatures wants a column of lists of 'name[:value]' strings "
+                         "with plain decimal values")
+    return sig
+
+
+def minhashes_batch(col, num_hashes: int = 5, key_groups: int = 2, device=None) -> list:
+    """``[minhashes(row, False, num_hashes, key_groups) for row in col]`` in one native pass."""
+    from ..ops import minhash as mh
+
+    nh, kg = int(num_hashes), int(key_groups)
+    sig = _column_signatures(col, nh * kg, device) if _engine_range(nh, kg) else None
+    if sig is None:
+        return [minhashes(r, False, nh, kg) for r in _rows_of(col)]
+    return mh.cluster_ids(sig, kg).cpu().numpy().tolist()
+
+
+def bbit_minhash_batch(col, num_hashes: int = 128, b: int = 1, device=None) -> list:
+    """``[bbit_minhash(row, num_hashes, b) for row in col]`` in one native pass."""
+    from ..ops import minhash as mh
+
+    nh, bb = int(num_hashes), int(b)
+    sig = _column_signatures(col, nh, device) if _engine_range(nh) and 1 <= bb <= 32 else None
+    if sig is None:
+        return [bbit_minhash(r, nh, bb) for r in _rows_of(col)]
+    return mh.bbit_pack(sig, bb)
+
+
+def _rows_of(col):
+    if hasattr(col, "to_pylist"):
+        return col.to_pylist()
+    return col.tolist() if hasattr(col, "tolist") else list(col)
+
+
+def _session_device(session):
+    return None if session is None else session.device
+
+
+def _minhash_batch(item, features, options=None, session=None):
+    """Column-at-once ``minhash(item, features [, options])``: ``(rows_idx, [clusterid, item])``,
+    or None (-> the per-row path) for a non-constant option string, a ``-n * -k`` product outside
+    the engine's range or a feature column the engine does not take."""
+    nh, kg = 5, 2
+    if options is not None:
+        if isinstance(options, str):
+            ops = {options}
+        else:
+            try:
+                ops = set(options)
+            except TypeError:
+                return None
+        if len(ops) != 1:
+            return None
+        options = ops.pop()
+        if options:
+            try:
+                toks = str(options).split()
+                if "-n" in toks:
+                    nh = int(toks[toks.index("-n") + 1])
+                if "-k" in toks:
+                    kg = int(toks[toks.index("-k") + 1])
+            except (ValueError, IndexError):
+                return None                      # the per-row path raises it
+    if not _engine_range(nh, kg):
+        return None
+    from ..ops import minhash as mh
+
+    sig = _column_signatures(features, nh * kg, _session_device(session))
+    if sig is None:
+        return None
+    ids = mh.cluster_ids(sig, kg).cpu().numpy()
+    items = _rows_of(item)
+    if len(items) != ids.shape[0]:
+        return None
+    rows_idx = np.repeat(np.arange(ids.shape[0], dtype=np.int64), nh)
+    return rows_idx, [ids.reshape(-1).astype(np.int64).tolist(), [items[i] for i in rows_idx]]
+
+
+_minhash_batch.wants_session = True
+minhash.batch = _minhash_batch
+minhash.batch_select = True        # also taken by SELECT minhash(...) (sql/executor._select_udtf)
+
+
+def _udf_column(features):
+    """(column, NULL mask) of a UDF's first argument when it is a whole column, else None."""
+    import pandas as pd
+
+    if not isinstance(features, pd.Series):
+        return None
+    if isinstance(features.dtype, pd.ArrowDtype):
+        return features, features.isna().to_numpy()
+    vals = features.tolist()
+    return vals, np.fromiter((v is None for v in vals), dtype=bool, count=len(vals))
+
+
+def _udf_result(vals: list, null, null_first: bool):
+    import pandas as pd
+
+    if null_first and null.any():
+        vals = [None if m else v for v, m in zip(vals, null)]
+    return pd.Series(vals, dtype=object).infer_objects() if vals else pd.Series([], dtype=object)
+
+
+def _const_int(v):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        raise TypeError
+    return int(v)
+
+
+def _minhashes_udf_batch(features, no_weight=False, num_hashes=5, key_groups=2, session=None,
+                         null_first=True):
+    """Column-at-once ``minhashes``: a Series, or None (-> the per-row path) unless the features
+    are a column and the other arguments int constants in the engine's range.  ``null_first``:
+    rows whose features are NULL stay NULL (the SQL rule for a NULL first argument)."""
+    from ..ops import minhash as mh
+
+    cm = _udf_column(features)
+    try:
+        nh, kg = _const_int(num_hashes), _const_int(key_groups)
+    except TypeError:
+        return None
+    if cm is None or not _engine_range(nh, kg):
+        return None
+    sig = _column_signatures(cm[0], nh * kg, _session_device(session))
+    if sig is None:
+        return None
+    return _udf_result(mh.cluster_ids(sig, kg).cpu().numpy().tolist(), cm[1], null_first)
+
+
+def _bbit_minhash_udf_batch(features, num_hashes=128, b=1, session=None, null_first=True):
+    """Column-at-once ``bbit_minhash``; see ``_minhashes_udf_batch``."""
+    from ..ops import minhash as mh
+
+    cm = _udf_column(features)
+    try:
+        nh, bb = _const_int(num_hashes), _const_int(b)
+    except TypeError:
+        return None
+    if cm is None or not _engine_range(nh) or not 1 <= bb <= 32:
+        return None
+    sig = _column_signatures(cm[0], nh, _session_device(session))
+    if sig is None:
+        return None
+    return _udf_result(mh.bbit_pack(sig, bb), cm[1], null_first)
+
+
+minhashes.batch = _minhashes_udf_batch
+bbit_minhash.batch = _bbit_minhash_udf_batch
+
+
 # ------------------------------------------------------------------ top-k
 @udtf("each_top_k", per_row=False)
 def each_top_k(k, group, score, *cols):

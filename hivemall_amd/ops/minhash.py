@@ -1,0 +1,248 @@
+"""MinHash signatures over packed feature strings (``csrc/kernels/minhash.hip``,
+``csrc/host/minhash_cpu.cpp``): the engine behind ``knn.minhash`` / ``minhashes`` /
+``bbit_minhash``.
+
+Contract: for row ``r`` and hash ``h`` in ``0..H-1``, ``sig[r, h]`` is the unsigned minimum over
+the row's feature names of ``MurmurHash3_x86_32(utf8(name), seed = (seed0 + h) mod 2^32)``; an
+empty row gives 0; duplicated names, values and weights change nothing.  The name of a feature
+string is everything before its first ``:`` (``knn._fv``).
+
+The input is a packed list<string> column: ``buf`` (uint8 bytes), ``off`` (int64 [nnz + 1] string
+offsets), ``nlen`` (int32 [nnz] name lengths) and ``rowptr`` (int64 [n_rows + 1] strings per row);
+``pack_feature_column`` builds it from Python lists or an Arrow column.  The result is int32
+``[n_rows, H]`` holding the uint32 bit patterns.  ``cuda`` tensors run the gfx950 kernel on the
+current stream, CPU tensors the OpenMP twin; both are integer only and agree bit for bit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import operator
+
+import numpy as np
+import torch
+
+from .. import _native
+
+_P = C.c_void_p
+_I64 = _native.c_i64
+_native.register_hip("hm_minhash_sig", [_P, _P, _P, _P, _I64, C.c_int, C.c_uint32, _P, _P])
+_native.register_host("hm_minhash_sig_cpu", [_P, _P, _P, _P, _I64, C.c_int, C.c_uint32, _P])
+_native.register_host("hm_minhash_names", [_P, _P, _I64, _P], restype=_I64)
+
+H_MAX = 1024
+# the kernel's tiling (csrc/kernels/minhash.hip); the result depends on none of them
+ROWS_PER_WG = 16        # MH_ROWS
+FEATS_PER_PASS = 256    # MH_FEATS
+BYTES_STAGED = 8192     # MH_BYTES
+HASHES_PER_PASS = 256   # MH_HASHES
+MAX_GRID = 4096         # MH_MAX_GRID
+
+
+def _want(t, name: str, dtype, ndim: int) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"minhash: {name} must be a torch tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise ValueError(f"minhash: {name} must be {dtype}, got {t.dtype}")
+    if t.dim() != ndim:
+        raise ValueError(f"minhash: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
+
+
+def _int_in(v, name: str, lo: int, hi: int) -> int:
+    try:
+        if isinstance(v, bool):
+            raise TypeError
+        v = operator.index(v)
+    except TypeError:
+        raise ValueError(f"minhash: {name} must be an int in {lo}..{hi}, got {v!r}") from None
+    if not lo <= v <= hi:
+        raise ValueError(f"minhash: {name} must be in {lo}..{hi}, got {v}")
+    return v
+
+
+def _check_ptr(p: torch.Tensor, name: str) -> None:
+    if p.numel() < 1:
+        raise ValueError(f"minhash: {name} must hold at least one offset")
+    if int(p[0]) != 0:
+        raise ValueError(f"minhash: {name} must start at 0, got {int(p[0])}")
+    if p.numel() > 1 and bool((p[1:] < p[:-1]).any()):
+        raise ValueError(f"minhash: {name} must be non-decreasing")
+
+
+def _pad16(buf: torch.Tensor) -> torch.Tensor:
+    """The kernel stages bytes in whole aligned 16-B chunks: a base that is 16-B aligned and a
+    length that is a multiple of 16 keep every such chunk inside the allocation."""
+    n = buf.numel()
+    if n and n % 16 == 0 and buf.data_ptr() % 16 == 0:
+        return buf
+    out = torch.zeros(max(16, (n + 15) // 16 * 16), dtype=torch.uint8, device=buf.device)
+    out[:n] = buf
+    return out
+
+
+def minhash_signatures(buf: torch.Tensor, off: torch.Tensor, nlen: torch.Tensor, rowptr: torch.Tensor,
+                       num_hashes: int, seed0: int = 0, *, check: bool = True) -> torch.Tensor:
+    """int32 [n_rows, num_hashes]: the minhash signature of every row (uint32 bit patterns).
+    ``check=False`` skips the passes over ``off``, ``nlen`` and ``rowptr`` (monotone offsets, name
+    lengths inside their strings) for a caller that built them itself, as ``pack_feature_column``
+    does; dtypes, shapes, devices and the two scalars are always checked."""
+    _want(buf, "buf", torch.uint8, 1)
+    _want(off, "off", torch.int64, 1)
+    _want(nlen, "nlen", torch.int32, 1)
+    _want(rowptr, "rowptr", torch.int64, 1)
+    for t, nm in ((off, "off"), (nlen, "nlen"), (rowptr, "rowptr")):
+        if t.device != buf.device:
+            raise ValueError(f"minhash: {nm} is on {t.device}, buf on {buf.device}")
+    H = _int_in(num_hashes, "num_hashes", 1, H_MAX)
+    seed0 = _int_in(seed0, "seed0", 0, 2**32 - 1)
+    if check:
+        _check_ptr(off, "off")
+        _check_ptr(rowptr, "rowptr")
+    elif off.numel() < 1 or rowptr.numel() < 1:
+        raise ValueError("minhash: off and rowptr must hold at least one offset")
+    nnz = off.numel() - 1
+    if nlen.numel() != nnz:
+        raise ValueError(f"minhash: nlen must hold {nnz} lengths (off has {nnz + 1} offsets), "
+                         f"got {nlen.numel()}")
+    if check and int(off[-1]) > buf.numel():
+        raise ValueError(f"minhash: off ends at {int(off[-1])}, buf holds {buf.numel()} bytes")
+    if check and int(rowptr[-1]) != nnz:
+        raise ValueError(f"minhash: rowptr must end at nnz = {nnz}, got {int(rowptr[-1])}")
+    if check and nnz and bool(((nlen < 0) | (nlen.long() > off[1:] - off[:-1])).any()):
+        raise ValueError("minhash: nlen[s] must be in 0..off[s + 1] - off[s]")
+    n_rows = rowptr.numel() - 1
+    dev = buf.device
+    out = torch.empty((n_rows, H), dtype=torch.int32, device=dev)
+    if n_rows == 0:
+        return out
+    buf, off, nlen, rowptr = (t.contiguous() for t in (buf, off, nlen, rowptr))
+    p = _native.ptr
+    if buf.is_cuda:
+        buf = _pad16(buf)
+        rc = _native.hip().hm_minhash_sig(p(buf), p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out),
+                                          _native.stream_of(dev))
+        _native.check(rc, "hm_minhash_sig")
+    else:
+        if buf.numel() == 0:
+            buf = torch.zeros(1, dtype=torch.uint8)
+        rc = _native.host().hm_minhash_sig_cpu(p(buf), p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out))
+        if rc != 0:
+            raise RuntimeError(f"hm_minhash_sig_cpu failed: {rc}")
+    return out
+
+
+def cluster_ids(sig: torch.Tensor, key_groups: int) -> torch.Tensor:
+    """int32 [n_rows, H / key_groups]: every run of ``key_groups`` hashes folded as ``minhashes``
+    does it, ``h = (h * 31 + v) & 0x7FFFFFFF`` over the unsigned ``v``, starting from 0."""
+    _want(sig, "sig", torch.int32, 2)
+    H = sig.shape[1]
+    kg = _int_in(key_groups, "key_groups", 1, max(H, 1))
+    if H % kg:
+        raise ValueError(f"minhash: key_groups = {kg} does not divide the {H} hashes of sig")
+    v = (sig.long() & 0xFFFFFFFF).reshape(sig.shape[0], H // kg, kg)
+    h = torch.zeros(v.shape[:2], dtype=torch.int64, device=sig.device)
+    for j in range(kg):
+        h = (h * 31 + v[:, :, j]) & 0x7FFFFFFF
+    return h.to(torch.int32)
+
+
+def bbit_pack(sig: torch.Tensor, b: int) -> list:
+    """The hex strings of ``bbit_minhash``: the lowest ``b`` bits of hash ``i`` at bit ``i * b``."""
+    _want(sig, "sig", torch.int32, 2)
+    b = _int_in(b, "b", 1, 32)
+    n, H = sig.shape
+    if n == 0 or H == 0:
+        return ["0"] * n
+    v = sig.cpu().numpy().view(np.uint32)
+    shifts = np.arange(b, dtype=np.uint32)
+    out = []
+    step = max(1, (1 << 24) // (H * b))                  # rows per piece: the bit image stays small
+    for r0 in range(0, n, step):
+        bits = ((v[r0:r0 + step, :, None] >> shifts) & 1).astype(np.uint8)        # [rows, H, b]
+        packed = np.packbits(bits.reshape(bits.shape[0], -1), axis=1, bitorder="little")
+        out.extend(format(int.from_bytes(row.tobytes(), "little"), "x") for row in packed)
+    return out
+
+
+# ------------------------------------------------------------------ packing a column
+def _arrow_list_of_strings(arr):
+    """One pyarrow list<string> array for ``arr`` or None when it is anything else."""
+    import pyarrow as pa
+
+    if isinstance(arr, pa.ChunkedArray):
+        if arr.num_chunks == 0:
+            return None
+        arr = arr.chunk(0) if arr.num_chunks == 1 else arr.combine_chunks()
+        if isinstance(arr, pa.ChunkedArray):
+            return None
+    ty = arr.type
+    if not (pa.types.is_list(ty) or pa.types.is_large_list(ty)):
+        return None
+    vt = ty.value_type
+    if pa.types.is_null(vt):
+        if len(arr.values) != 0:
+            return None                                   # lists of NULLs
+        return arr.cast(pa.list_(pa.string()))
+    if not (pa.types.is_string(vt) or pa.types.is_large_string(vt)):
+        return None
+    if arr.values.null_count:
+        return None                                       # a NULL feature inside a row
+    return arr
+
+
+def _null_rows_are_empty(arr) -> bool:
+    if arr.null_count == 0:
+        return True
+    lo = np.asarray(arr.offsets, dtype=np.int64)
+    valid = np.asarray(arr.is_valid())
+    return bool(((lo[1:] - lo[:-1])[~valid] == 0).all())
+
+
+def pack_feature_column(col):
+    """``(buf uint8, off int64 [nnz + 1], nlen int32 [nnz], rowptr int64 [n_rows + 1])`` CPU tensors
+    for a column of feature-string lists (a sequence / pandas Series of lists of ``str``, or an
+    Arrow list<string>); a NULL row counts as an empty row.  None when the column holds anything
+    else (ints, dicts, numeric arrays, NULL features) or a ``name:value`` whose value text is not
+    a plain decimal: those keep the per-row functions and whatever they raise."""
+    import pandas as pd
+    import pyarrow as pa
+
+    from ..io.ingest import arrow_buffers
+
+    arr = col
+    if isinstance(arr, pd.Series):
+        arr = arr.array._pa_array if isinstance(arr.dtype, pd.ArrowDtype) else arr.tolist()
+    if not isinstance(arr, (pa.Array, pa.ChunkedArray)):
+        if isinstance(arr, np.ndarray):
+            arr = arr.tolist()
+        if not isinstance(arr, (list, tuple)):
+            return None
+        for r in arr:                                     # pyarrow would read a str as a list of chars
+            if r is not None and not isinstance(r, (list, tuple)):
+                return None
+        if len(arr) == 0:
+            arr = pa.array([], type=pa.list_(pa.string()))
+        else:
+            try:
+                arr = pa.array(arr)                       # inferred: mixed or non-string rows fail or differ
+            except (pa.ArrowInvalid, pa.ArrowTypeError, pa.ArrowNotImplementedError, UnicodeError,
+                    OverflowError):
+                return None
+    arr = _arrow_list_of_strings(arr)
+    if arr is None:
+        return None
+    if not _null_rows_are_empty(arr):
+        arr = pa.array([[] if r is None else r for r in arr.to_pylist()], type=arr.type)
+    data, so, lo = arrow_buffers(arr)
+    nnz = len(so) - 1
+    if len(lo) == 0 or int(lo[-1]) != nnz:
+        return None
+    buf = np.ascontiguousarray(data) if len(data) else np.zeros(1, np.uint8)
+    so = np.ascontiguousarray(so, dtype=np.int64)
+    nlen = np.empty(nnz, dtype=np.int32)
+    bad = int(_native.host().hm_minhash_names(buf.ctypes.data, so.ctypes.data, nnz, nlen.ctypes.data))
+    if bad != -1:
+        return None
+    if not buf.flags.writeable:
+        buf = buf.copy()                                  # torch wants a writable array
+    return (torch.from_numpy(buf[:len(data)] if len(data) else buf[:0]), torch.from_numpy(so),
+            torch.from_numpy(nlen), torch.from_numpy(np.ascontiguousarray(lo, dtype=np.int64)))

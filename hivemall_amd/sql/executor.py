@@ -893,7 +893,7 @@ class Session:
         if per_row and batch is not None and not lv.outer and os.environ.get("HM_SQL_BATCH_UDTF", "1") != "0":
             # column-at-once form of a per-row UDTF (e.g. feature_pairs '-ffm'): same rows, same
             # order, no Python generator per input row
-            res = batch(*args)
+            res = batch(*args, **({"session": self} if getattr(batch, "wants_session", False) else {}))
             if res is not None:
                 rows_idx, cols = res
                 names = lv.col_aliases or list(default_cols or [f"col{i}" for i in range(len(cols))])
@@ -1106,6 +1106,19 @@ class Session:
         else:
             args = [_ser(self.eval(a, src, ctes), src.n).tolist() for a in f.args]
         if per_row:
+            batch = getattr(impl, "batch", None)
+            if batch is not None and getattr(impl, "batch_select", False) and \
+                    os.environ.get("HM_SQL_BATCH_UDTF", "1") != "0":
+                # column-at-once form of a per-row UDTF that opts in (minhash): same rows, same order
+                res = batch(*args, **({"session": self} if getattr(batch, "wants_session", False) else {}))
+                if res is not None:
+                    _, cols = res
+                    names = item.aliases or ([item.alias] if item.alias else None) or \
+                        list(default_cols or [f"col{i}" for i in range(len(cols))])
+                    nout = len(cols[0]) if cols else 0
+                    data = {f"c{i}": cols[i] if i < len(cols) else [None] * nout for i in range(len(names))}
+                    return Frame(pd.DataFrame(data, columns=[f"c{i}" for i in range(len(names))]),
+                                 [(None, n) for n in names])
             rows = []
             for r in range(src.n):
                 rows.extend(tuple(t) for t in impl(*[a[r] for a in args]))
@@ -1517,6 +1530,13 @@ class Session:
                 kwargs = {"session": self} if getattr(fd.impl, "wants_session", False) else {}
                 res = fd.impl(*[_ser(a, n) if isinstance(a, pd.Series) else a for a in args], **kwargs)
                 return _ser(res if not isinstance(res, list) else pd.Series(res, dtype=object), n)
+            batch = getattr(fd.impl, "batch", None)
+            if batch is not None and os.environ.get("HM_SQL_BATCH_UDTF", "1") != "0":
+                # column-at-once form of a per-row UDF that opts in (minhashes, bbit_minhash): whole
+                # columns for column arguments, constants as they are; None -> the per-row loop
+                res = batch(*[_ser(a, n) if isinstance(a, pd.Series) else a for a in args], session=self)
+                if res is not None:
+                    return _ser(res, n)
             cols = [_ser(a, n).tolist() if isinstance(a, pd.Series) else None for a in args]
             out = []
             # Hivemall's UDFs return NULL for a NULL principal (first) argument: such rows yield
