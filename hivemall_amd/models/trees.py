@@ -39,16 +39,16 @@ MODEL_VERSION = 1
 CAT_FLAG = 1 << 30   # nominal split flag in flattened node arrays (HM_TREE_CAT in trees.hip)
 DLEFT_FLAG = 1 << 29  # missing values go left at this split (HM_TREE_DLEFT)
 HIST_BLOCKS = 256    # histogram grid (blocks per feature group); benchmarks/hist_sweep.py, profiles/hist_sweep_r1.jsonl
-HIST_WIDE = os.environ.get("HM_HIST_WIDE", "1") == "1"   # all-features single-pass histogram
-ROUTE_FUSED = os.environ.get("HM_ROUTE_FUSED", "1") == "1"  # route + small-child count in one pass
-ROUTE_COLS = os.environ.get("HM_ROUTE_COLS", "1") == "1"    # routing reads a feature-major bins copy
-# heap trees: the last level's leaf statistics from the split search, not from histograms
-LAST_FROM_SPLITS = os.environ.get("HM_TREE_LAST_FROM_SPLITS", "1") == "1"
-ROUTE_GRID = int(os.environ.get("HM_ROUTE_GRID", "2048"))   # blocks of the fused route + count pass
-GBT2 = os.environ.get("HM_GBT2", "1") == "1"    # GBT histograms of (r, w), Newton leaves summed per leaf
-HEAP_TREES = os.environ.get("HM_TREE_HEAP", "1") == "1"   # fixed-shape levels, no per-level host read
+HIST_WIDE_BLOCKS = 256   # grid of the all-features single-pass histogram
+ROUTE_GRID = 2048        # blocks of the fused route + count pass (see _route_partition_gpu)
+PARTITION_MAX_KEYS = 8192    # most keys hm_partition_count / _scatter / hm_route_count take
+LEAF_SUMS_MAX_NODES = 8192   # most nodes hm_leaf_sums takes
 HEAP_MAX_DEPTH = 10
-HIST_WIDE_BLOCKS = int(os.environ.get("HM_HIST_WIDE_BLOCKS", "256"))
+# The switches that select a level loop of HistTreeBuilder.build, which reads them once per tree.
+ROUTE_FUSED = os.environ.get("HM_ROUTE_FUSED", "1") == "1"  # route + small-child count in one pass
+# fused trees: the last level's leaf statistics from the split search, not from histograms
+LAST_FROM_SPLITS = os.environ.get("HM_TREE_LAST_FROM_SPLITS", "1") == "1"
+HEAP_TREES = os.environ.get("HM_TREE_HEAP", "1") == "1"   # fixed-shape levels, no per-level host read
 
 
 # ------------------------------------------------------------------ quantisation
@@ -83,7 +83,7 @@ class Quantized:
         """(bins pointer, column stride) for the routing kernels: the feature-major copy
         [d, n] on a GPU (built once per matrix; a wave's rows then read one 64-B run per distinct
         split feature instead of their whole 32-B rows), else row-major (stride 0)."""
-        if not (ROUTE_COLS and self.bins.is_cuda):
+        if not self.bins.is_cuda:
             return _native.ptr(self.bins), 0
         if self._bins_t is None:
             self._bins_t = self.bins[:, : self.d].t().contiguous()
@@ -253,7 +253,7 @@ def predict_forest(trees: list[Tree], X: torch.Tensor, sum_trees: bool = True,
 
 
 class _NodeBuf:
-    """Growable device arrays of one tree's nodes (GPU builder): flagged split feature, split
+    """Growable device arrays of one tree's nodes: flagged split feature, split
     bin, children, threshold and leaf values, indexed by node id.  The routing kernel reads them
     as they stand, so no per-level concatenation is needed."""
 
@@ -276,6 +276,32 @@ class _NodeBuf:
                 t[:self.cap] = old
             setattr(self, k, t)
         self.cap = cap
+
+
+@dataclass
+class _TreeState:
+    """One tree while HistTreeBuilder.build grows it.  The current level is nodes
+    [base, base + L) at ``depth``."""
+    stats: torch.Tensor           # f32 [n, NS]
+    smax: torch.Tensor            # the columns' |max|
+    node_of_row: torch.Tensor     # node id of every row (-1: inactive); int16 in the heap layout
+    act_rows: torch.Tensor        # int32 ids of the rows with non-zero statistics
+    identity_rows: bool           # act_rows is 0 .. n-1
+    edges: torch.Tensor
+    imp: torch.Tensor             # f64 [d] split-gain importance
+    nodes: _NodeBuf
+    fused: bool                   # the level's bookkeeping runs on the GPU (hm_level_finalize)
+    heap: bool                    # fused, fixed-shape levels
+    route_fused: bool             # the module switches, as they stood when the tree was started
+    last_from_splits: bool
+    arena: torch.Tensor | None = None   # heap: every level's smaller-child histograms
+    n_leaves: int = 1             # tensor loop: leaves so far, against max_leaf_nodes
+    base: int = 0
+    L: int = 1
+    depth: int = 0
+
+    def descend(self, n_pairs: int) -> None:
+        self.base, self.L, self.depth = self.base + self.L, 2 * n_pairs, self.depth + 1
 
 
 class HistTreeBuilder:
@@ -506,7 +532,7 @@ class HistTreeBuilder:
             nblk = HIST_BLOCKS
             # (hm_hist_build instantiates the one-pass kernel for NS <= 4; 5..8 statistics take
             # the feature-group kernel)
-            if HIST_WIDE and NS <= 4 and q.d <= 32 and q.dpad % 32 == 0 and q.d * q.B * NS * 4 <= 160 * 1024:
+            if NS <= 4 and q.d <= 32 and q.dpad % 32 == 0 and q.d * q.B * NS * 4 <= 160 * 1024:
                 FG, nblk = 32, HIST_WIDE_BLOCKS
             args = (p(q.bins), q.d, q.dpad, q.B, p(rows), p(seg), n_seg, p(stats), p(smax), NS, FG, p(hist))
             if dev.type == "cuda":
@@ -518,14 +544,196 @@ class HistTreeBuilder:
             self.mixer.all_reduce_sum([hist])
         return hist
 
+    def _route(self, node_of_row, lo: int, hi: int, sf, sb, lc, rc):
+        """Every row one level down: the rows of the splitting nodes among [lo, hi) move to their
+        child by the split's bin (hm_route_rows; leaves keep their id, split feature < 0)."""
+        q = self.q
+        p = _native.ptr
+        n = C.c_int64(node_of_row.numel())
+        rest = (p(node_of_row), p(sf), p(sb), p(lc), p(rc), (q.B - 1) if self.missing else -1)
+        if node_of_row.is_cuda:
+            src, cs = q.route_src()
+            _native.check(_native.hip().hm_route_rows(
+                src, n, q.dpad, C.c_int64(cs), lo, hi, *rest, int(node_of_row.dtype == torch.int16),
+                _native.stream_of(node_of_row.device)), "hm_route_rows")
+        else:
+            _native.host().hm_route_rows_cpu(p(q.bins), n, q.dpad, *rest)
+
+    def _small_child_rows(self, s: "_TreeState", lut, n_keys: int):
+        """Route the level's rows, then group those that reached the smaller child of a split:
+        (rows, seg) with child k's rows at rows[seg[k]:seg[k + 1]].  ``lut`` maps a child's id
+        relative to the next level's first node to its key (32767: not histogrammed)."""
+        t, nb = s.nodes, s.base + s.L
+        counting = s.node_of_row.is_cuda and n_keys <= PARTITION_MAX_KEYS
+        if counting and s.fused and s.identity_rows and s.route_fused:
+            return self._route_partition_gpu(s.node_of_row.numel(), s.node_of_row, t, nb, lut, n_keys, s.base)
+        self._route(s.node_of_row, s.base, nb, t.sf, t.sb, t.lc, t.rc)
+        if counting:
+            return self._partition_gpu(s.act_rows, s.node_of_row, nb, lut, n_keys)
+        # CPU, or more keys than the counting sort takes: a stable sort of every active row
+        nr = s.node_of_row[s.act_rows.long()] - nb
+        key = torch.where(nr >= 0, lut[nr.clamp_min(0).long()], torch.full_like(nr, 32767, dtype=torch.int16))
+        skey, order = torch.sort(key, stable=True)
+        seg = torch.searchsorted(skey, torch.arange(n_keys + 1, device=key.device, dtype=torch.int16))
+        return s.act_rows[order].contiguous(), seg.to(torch.int64)
+
+    def _children_hists(self, s: "_TreeState", H, rows, seg, n_pairs: int, li, small_right, out=None):
+        """Histograms [2 * n_pairs, d, B, NS] of the next level: the smaller child of every pair
+        from its rows (into ``out`` when given), its sibling as parent - child.  ``li``: the
+        parents' indices in H; None in the heap layout, where pair l belongs to parent l and a
+        parent that did not split leaves two empty slots.  ``small_right`` uint8 [n_pairs]."""
+        Hs = self._hist(rows, seg.contiguous(), n_pairs, s.stats, s.smax, out=out)
+        Hn = torch.empty((2 * n_pairs, *H.shape[1:]), dtype=torch.float32, device=H.device)
+        if not H.is_cuda:
+            sr = small_right.long()
+            j2 = 2 * torch.arange(n_pairs, device=H.device)
+            Hn[j2 + sr] = Hs
+            Hn[j2 + 1 - sr] = H[li] - Hs
+            return Hn
+        p, st = _native.ptr, _native.stream_of(H.device)
+        per = C.c_int64(math.prod(H.shape[1:]))            # d * B * NS floats per node
+        if li is None:
+            _native.check(_native.hip().hm_hist_sibling_heap(
+                p(H), p(Hs), p(s.nodes.sf) + 4 * s.base, p(small_right), per, n_pairs, p(Hn), st),
+                "hm_hist_sibling_heap")
+        else:
+            _native.check(_native.hip().hm_hist_sibling(
+                p(H), p(Hs), p(li), p(small_right), per, n_pairs, p(Hn), st), "hm_hist_sibling")
+        return Hn
+
+    def _close_level_as_leaves(self, s: "_TreeState", H) -> None:
+        """The level at max_depth: its nodes are leaves valued from their histograms."""
+        t, lo, hi = s.nodes, s.base, s.base + s.L
+        t.ensure(hi)
+        t.vals[lo:hi] = self._leaf_values(H[:, 0].sum(1))
+        t.sf[lo:hi] = -1
+        t.thr[lo:hi] = math.inf
+        t.lc[lo:hi] = -1
+        t.rc[lo:hi] = -1
+
+    def _fused_level(self, s: "_TreeState", H):
+        """One level of the GPU builder: split search and the level's bookkeeping in two kernels,
+        written into the node buffer.  The heap layout has a fixed shape (L = 2^depth node slots,
+        pair l = the children of parent l): nothing is read on the host and the next level's
+        kernels queue behind this one's.  The compact layout numbers only the children of the
+        nodes that split and reads their count.  Returns the next level's histograms, or None
+        when the tree is complete."""
+        t, lo, nb = s.nodes, s.base, s.base + s.L
+        gain, bf, braw, left, tot = self._split_find_raw(H, lo)
+        last = s.last_from_splits and s.depth + 1 >= self.max_depth
+        fin = self._level_finalize(gain, bf, braw, left, tot, lo, nb, s.edges, t, s.imp, heap=s.heap, last=last)
+        if s.heap:
+            (small_right, lut), li, n_pairs = fin, None, s.L
+        else:
+            li, small_right, lut, n_pairs = fin
+            if n_pairs == 0:
+                return None
+        if last:
+            # the children are leaves: hm_level_finalize wrote their records from the split search
+            # (left, total - left), so the rows are routed and nothing is partitioned or histogrammed
+            self._route(s.node_of_row, lo, nb, t.sf, t.sb, t.lc, t.rc)
+            Hn = None
+        else:
+            rows, seg = self._small_child_rows(s, lut, n_pairs)
+            out = None
+            if s.heap:
+                if s.arena is None:   # every level's smaller-child histograms, zeroed in one fill
+                    # levels 0 .. max_depth - 1 histogram L = 2^depth children into slots
+                    # [L - 1, 2L - 1); with last_from_splits the last split level histograms nothing
+                    top = self.max_depth - (1 if s.last_from_splits else 0)
+                    s.arena = torch.zeros(((1 << top) - 1, *H.shape[1:]), dtype=torch.float32, device=H.device)
+                out = s.arena[s.L - 1:2 * s.L - 1]
+            Hn = self._children_hists(s, H, rows, seg, n_pairs, li, small_right, out=out)
+        s.descend(n_pairs)
+        return Hn
+
+    def _tensor_level(self, s: "_TreeState", H):
+        """One level with the bookkeeping in torch (CPU tensors, ``max_leaf_nodes``).  Returns
+        like :meth:`_fused_level`."""
+        t, dev, edges = s.nodes, H.device, s.edges
+        lo, nb = s.base, s.base + s.L
+        best_gain, bf, bb, left_all, tot, bdl = self._split_find(H, lo)
+        ok = (best_gain > max(1e-12, self.min_gain)) & torch.isfinite(best_gain) & \
+            (self._weight(tot) >= self.min_split)
+        if self.max_leaves is not None:
+            ok &= torch.cumsum(ok.long(), 0) <= int(self.max_leaves) - s.n_leaves
+        li = torch.nonzero(ok).flatten()                                   # the level's one sync
+        n_split = li.numel()
+        rank = torch.cumsum(ok.int(), 0) - 1
+        lc = torch.where(ok, nb + 2 * rank, torch.full_like(rank, -1)).to(torch.int32)
+        thr = torch.where(bb < edges.shape[1], edges[bf.long(), bb.clamp(max=edges.shape[1] - 1).long()],
+                          torch.full_like(best_gain, math.inf))
+        cat = self._masks[1]                                               # uint8 [d] on the device
+        bflag = bf if cat is None else bf | (cat[bf.long()].to(torch.int32) * CAT_FLAG)
+        bflag = bflag | (bdl * DLEFT_FLAG)
+        t.ensure(nb)
+        t.vals[lo:nb] = self._leaf_values(tot)
+        t.sf[lo:nb] = torch.where(ok, bflag, torch.full_like(bf, -1))
+        t.thr[lo:nb] = torch.where(ok, thr, torch.full_like(thr, math.inf))
+        rc = torch.where(ok, lc + 1, lc)
+        t.lc[lo:nb] = lc
+        t.rc[lo:nb] = rc
+        t.sb[lo:nb] = bb
+        if n_split == 0:
+            return None
+        s.imp.index_add_(0, bf[li].long(), best_gain[li].double())
+        s.n_leaves += n_split
+        # next level: histogram the smaller child of every split, derive the sibling
+        left_tot = left_all[li]                                            # [S, NS]
+        right_tot = tot[li] - left_tot
+        small_right = self._weight(right_tot) < self._weight(left_tot)     # [S]
+        small_id = torch.where(small_right, rc[li], lc[li]) - nb           # local child id
+        lut = torch.full((2 * n_split,), 32767, dtype=torch.int16, device=dev)
+        lut[small_id.long()] = torch.arange(n_split, device=dev, dtype=torch.int16)
+        rows, seg = self._small_child_rows(s, lut, n_split)
+        Hn = self._children_hists(s, H, rows, seg, n_split, li, small_right.to(torch.uint8))
+        s.descend(n_split)
+        return Hn
+
+    def _start_tree(self, stats, active, smax, act_rows, identity_rows) -> "_TreeState":
+        """The per-tree state at the root, with the module switches read once."""
+        dev = stats.device
+        n, NS = stats.shape
+        many_ok = NS <= 8 or self.criterion in ("gini", "entropy")   # hm_level_finalize's statistics
+        fused = dev.type == "cuda" and self.max_leaves is None and many_ok
+        # heap layout (no host read per level): shallow trees without per-node feature draws,
+        # whose node ids (the draw's key) would differ from the compact numbering
+        heap = (HEAP_TREES and fused and self.max_depth <= HEAP_MAX_DEPTH
+                and not (self.mtry is not None and self.mtry < self.q.d))
+        # heap levels hold at most 2^(HEAP_MAX_DEPTH + 1) - 1 node ids: int16 halves the bytes of
+        # the per-level routing / partition / leaf passes over the rows
+        node_of_row = torch.zeros(n, dtype=torch.int16 if heap else torch.int32, device=dev)
+        if active is not None:
+            node_of_row[~active] = -1
+        identity_rows = bool(identity_rows and active is None and act_rows is not None and act_rows.numel() == n)
+        if act_rows is None:
+            act = (stats != 0).any(1)
+            if active is not None:
+                act &= active
+            act_rows = torch.nonzero(act).flatten().to(torch.int32)
+        nodes = _NodeBuf(min(1 << 13, 2 << min(self.max_depth, 30)),
+                         NS if self.criterion in ("gini", "entropy") else 1, dev)
+        if smax is not None:
+            smax = smax.contiguous()
+        elif dev.type == "cuda" and NS <= 8:              # fixed-point range of the LDS sums
+            smax = torch.zeros(NS, dtype=torch.float32, device=dev)
+            _native.check(_native.hip().hm_absmax_cols(_native.ptr(stats), C.c_int64(n), NS, _native.ptr(smax),
+                                                        _native.stream_of(dev)), "hm_absmax_cols")
+        else:
+            smax = stats.abs().amax(0).contiguous()
+        return _TreeState(stats, smax, node_of_row, act_rows, identity_rows,
+                          self.q.edges.to(device=dev, dtype=torch.float32).contiguous(),
+                          torch.zeros(self.q.d, dtype=torch.float64, device=dev), nodes, fused, heap,
+                          ROUTE_FUSED, LAST_FROM_SPLITS)
+
     def build(self, stats: torch.Tensor, active: torch.Tensor | None = None, smax: torch.Tensor | None = None,
               act_rows: torch.Tensor | None = None, identity_rows: bool = False,
               leaf_h: torch.Tensor | None = None, defer: bool = False):
         """Grow one tree level by level.  stats: f32 [n, NS] per-row statistics.
 
         Every level: split search on the device over the level's histograms; one host sync
-        (the number of splits); rows routed by the bins; the next level histograms only the
-        smaller child of each split (sibling = parent - child).  After the call
+        (the number of splits; none in the heap layout); rows routed by the bins; the next level
+        histograms only the smaller child of each split (sibling = parent - child).  After the call
         ``self.leaf_of_row`` holds the leaf node id of every row (-1: inactive).  ``smax`` (the
         columns' |max|) and ``act_rows`` (int32 ids of the rows with non-zero stats) may be
         passed in when the caller already has them (the fused GBT statistics kernel);
@@ -535,273 +743,50 @@ class HistTreeBuilder:
         ``defer`` (level-fused builder): return a :class:`PendingTree` whose node arrays stay on
         the device (no host read at the end of the tree, importance left in ``imp_dev``) — the
         boosting loops materialise all trees after the last one."""
-        q = self.q
+        s = self._start_tree(stats.contiguous(), active, smax, act_rows, identity_rows)
         dev = stats.device
-        n, NS = stats.shape
-        d, B = q.d, q.B
-        stats = stats.contiguous()
-        identity_rows = bool(identity_rows and active is None and act_rows is not None and act_rows.numel() == n)
-        # heap layout (no host read per level): shallow trees without per-node feature draws,
-        # whose node ids (the draw's key) would differ from the compact numbering
-        heap = (HEAP_TREES and dev.type == "cuda" and self.max_leaves is None
-                and self.max_depth <= HEAP_MAX_DEPTH and not (self.mtry is not None and self.mtry < d)
-                and (NS <= 8 or self.criterion in ("gini", "entropy")))
-        # heap levels hold at most 2^(HEAP_MAX_DEPTH + 1) - 1 node ids: int16 halves the bytes of
-        # the per-level routing / partition / leaf passes over the rows
-        node_of_row = torch.zeros(n, dtype=torch.int16 if heap else torch.int32, device=dev)
-        arena = None
-        if active is not None:
-            node_of_row[~active] = -1
-        if act_rows is None:
-            act = (stats != 0).any(1)
-            if active is not None:
-                act &= active
-            act_rows = torch.nonzero(act).flatten().to(torch.int32)
-        edges = q.edges.to(device=dev, dtype=torch.float32).contiguous()
-        cat_dev = None if self.cat is None else self.cat.to(dev)
-        fused = dev.type == "cuda" and self.max_leaves is None and (NS <= 8 or self.criterion in ("gini", "entropy"))
-        n_out_ = NS if self.criterion in ("gini", "entropy") else 1
-        nbuf = _NodeBuf(min(1 << 13, 2 << min(self.max_depth, 30)), n_out_, dev) if fused else None
-        n_out = NS if self.criterion in ("gini", "entropy") else 1
-        imp = torch.zeros(d, dtype=torch.float64, device=dev)
         # level 0: the root histogram over every active row
         seg = torch.stack([torch.zeros((), dtype=torch.int64, device=dev),
-                           torch.full((), act_rows.numel(), dtype=torch.int64, device=dev)])
-        if smax is not None:
-            smax = smax.contiguous()
-        elif dev.type == "cuda" and NS <= 8:              # fixed-point range of the LDS sums
-            smax = torch.zeros(NS, dtype=torch.float32, device=dev)
-            _native.check(_native.hip().hm_absmax_cols(_native.ptr(stats), C.c_int64(n), NS, _native.ptr(smax),
-                                                        _native.stream_of(dev)), "hm_absmax_cols")
-        else:
-            smax = stats.abs().amax(0).contiguous()
-        H = self._hist(act_rows, seg, 1, stats, smax)
-        base, L = 0, 1
-        n_leaves = torch.ones((), dtype=torch.int64, device=dev)
-        feats, thrs, lefts, rights, vals = [], [], [], [], []
-        sf_all = torch.zeros(0, dtype=torch.int32, device=dev)
-        sb_all, lc_all, rc_all = sf_all.clone(), sf_all.clone(), sf_all.clone()
-        depth = 0
-        while True:
-            if depth >= self.max_depth and fused:
-                nbuf.ensure(base + L)
-                nbuf.vals[base:base + L] = self._leaf_values(H[:, 0].sum(1))
-                nbuf.sf[base:base + L] = -1
-                nbuf.thr[base:base + L] = math.inf
-                nbuf.lc[base:base + L] = -1
-                nbuf.rc[base:base + L] = -1
+                           torch.full((), s.act_rows.numel(), dtype=torch.int64, device=dev)])
+        H = self._hist(s.act_rows, seg, 1, s.stats, s.smax)
+        while H is not None:
+            if s.depth >= self.max_depth:
+                self._close_level_as_leaves(s, H)
                 break
-            if depth >= self.max_depth:
-                vals.append(self._leaf_values(H[:, 0].sum(1)))
-                feats.append(torch.full((L,), -1, dtype=torch.int32, device=dev))
-                thrs.append(torch.full((L,), math.inf, device=dev))
-                lefts.append(torch.full((L,), -1, dtype=torch.int32, device=dev))
-                rights.append(torch.full((L,), -1, dtype=torch.int32, device=dev))
-                break
-            if fused and heap:
-                # fixed-shape level (L = 2^depth node slots, heap numbering): nothing is read on
-                # the host, the next level's kernels queue behind this one's
-                gain, bf, braw, left_all, tot = self._split_find_raw(H, base)
-                nb = base + L
-                last = LAST_FROM_SPLITS and depth + 1 >= self.max_depth
-                sr, lut = self._level_finalize(gain, bf, braw, left_all, tot, base, nb, edges, nbuf, imp, heap=True,
-                                               last=last)
-                p = _native.ptr
-                if last:
-                    # the children are leaves: route the rows, and take the children's statistics
-                    # from the split search (left, total - left) instead of histogramming them
-                    # (no partition, histogram or sibling pass for the last level)
-                    src, cs = q.route_src()
-                    _native.check(_native.hip().hm_route_rows(
-                        src, C.c_int64(n), q.dpad, C.c_int64(cs), base, base + L, p(node_of_row), p(nbuf.sf), p(nbuf.sb),
-                        p(nbuf.lc), p(nbuf.rc), (q.B - 1) if self.missing else -1,
-                        int(node_of_row.dtype == torch.int16), _native.stream_of(dev)), "hm_route_rows")
-                    base, L = nb, 2 * L
-                    depth += 1
-                    break
-                if identity_rows and ROUTE_FUSED:
-                    rows, seg = self._route_partition_gpu(n, node_of_row, nbuf, nb, lut, L, base)
-                else:
-                    src, cs = q.route_src()
-                    _native.check(_native.hip().hm_route_rows(
-                        src, C.c_int64(n), q.dpad, C.c_int64(cs), base, base + L, p(node_of_row), p(nbuf.sf), p(nbuf.sb), p(nbuf.lc),
-                        p(nbuf.rc), (q.B - 1) if self.missing else -1, int(node_of_row.dtype == torch.int16),
-                        _native.stream_of(dev)), "hm_route_rows")
-                    rows, seg = self._partition_gpu(act_rows, node_of_row, nb, lut, L)
-                if arena is None:   # every level's smaller-child histograms, zeroed in one fill
-                    # levels 0 .. max_depth - 1 histogram L = 2^depth children into slots
-                    # [L - 1, 2L - 1); with LAST_FROM_SPLITS the last split level histograms nothing
-                    top = self.max_depth - (1 if LAST_FROM_SPLITS else 0)
-                    arena = torch.zeros((((1 << top) - 1), d, B, NS), dtype=torch.float32, device=dev)
-                Hs = self._hist(rows, seg.contiguous(), L, stats, smax, out=arena[L - 1:2 * L - 1])
-                Hn = torch.empty((2 * L, d, B, NS), dtype=torch.float32, device=dev)
-                _native.check(_native.hip().hm_hist_sibling_heap(
-                    p(H), p(Hs), p(nbuf.sf) + 4 * base, p(sr), C.c_int64(d * B * NS), L, p(Hn),
-                    _native.stream_of(dev)), "hm_hist_sibling_heap")
-                H = Hn
-                base, L = nb, 2 * L
-                depth += 1
-                continue
-            if fused:
-                gain, bf, braw, left_all, tot = self._split_find_raw(H, base)
-                nb = base + L
-                last = LAST_FROM_SPLITS and depth + 1 >= self.max_depth
-                li, small_right, lut, n_split = self._level_finalize(gain, bf, braw, left_all, tot, base, nb,
-                                                                     edges, nbuf, imp, last=last)
-                if n_split == 0:
-                    break
-                p = _native.ptr
-                if last:
-                    # children are leaves: route, and their statistics from the split search
-                    # (split k's children are nb + 2k, nb + 2k + 1)
-                    src, cs = q.route_src()
-                    _native.check(_native.hip().hm_route_rows(
-                        src, C.c_int64(n), q.dpad, C.c_int64(cs), base, base + L, p(node_of_row), p(nbuf.sf), p(nbuf.sb),
-                        p(nbuf.lc), p(nbuf.rc), (q.B - 1) if self.missing else -1,
-                        int(node_of_row.dtype == torch.int16), _native.stream_of(dev)), "hm_route_rows")
-                    base, L = nb, 2 * n_split
-                    depth += 1
-                    break
-                if identity_rows and n_split <= 8192 and ROUTE_FUSED:
-                    rows, seg = self._route_partition_gpu(n, node_of_row, nbuf, nb, lut, n_split, base)
-                    Hs = self._hist(rows, seg.contiguous(), n_split, stats, smax)
-                    Hn = torch.empty((2 * n_split, d, B, NS), dtype=torch.float32, device=dev)
-                    _native.check(_native.hip().hm_hist_sibling(
-                        _native.ptr(H), _native.ptr(Hs), _native.ptr(li), _native.ptr(small_right),
-                        C.c_int64(d * B * NS), n_split, _native.ptr(Hn), _native.stream_of(dev)), "hm_hist_sibling")
-                    H = Hn
-                    base, L = nb, 2 * n_split
-                    depth += 1
-                    continue
-                src, cs = q.route_src()
-                _native.check(_native.hip().hm_route_rows(
-                    src, C.c_int64(n), q.dpad, C.c_int64(cs), base, base + L, p(node_of_row), p(nbuf.sf), p(nbuf.sb), p(nbuf.lc), p(nbuf.rc),
-                    (q.B - 1) if self.missing else -1, int(node_of_row.dtype == torch.int16),
-                        _native.stream_of(dev)), "hm_route_rows")
-                if n_split <= 8192:
-                    rows, seg = self._partition_gpu(act_rows, node_of_row, nb, lut, n_split)
-                else:
-                    nr = node_of_row[act_rows.long()] - nb
-                    key = torch.where(nr >= 0, lut[nr.clamp_min(0).long()],
-                                      torch.full_like(nr, 32767, dtype=torch.int16))
-                    skey, order = torch.sort(key, stable=True)
-                    rows = act_rows[order].contiguous()
-                    seg = torch.searchsorted(skey, torch.arange(n_split + 1, device=dev, dtype=torch.int16)).to(torch.int64)
-                Hs = self._hist(rows, seg.contiguous(), n_split, stats, smax)
-                Hn = torch.empty((2 * n_split, d, B, NS), dtype=torch.float32, device=dev)
-                _native.check(_native.hip().hm_hist_sibling(
-                    _native.ptr(H), _native.ptr(Hs), _native.ptr(li), _native.ptr(small_right), C.c_int64(d * B * NS),
-                    n_split, _native.ptr(Hn), _native.stream_of(dev)), "hm_hist_sibling")
-                H = Hn
-                base, L = nb, 2 * n_split
-                depth += 1
-                continue
-            best_gain, bf, bb, left_all, tot, bdl = self._split_find(H, base)
-            vals.append(self._leaf_values(tot))
-            ok = (best_gain > max(1e-12, self.min_gain)) & torch.isfinite(best_gain) & \
-                (self._weight(tot) >= self.min_split)
-            if self.max_leaves is not None:
-                ok &= torch.cumsum(ok.long(), 0) <= (int(self.max_leaves) - n_leaves)
-            li = torch.nonzero(ok).flatten()                                   # the level's one sync
-            n_split = li.numel()
-            rank = torch.cumsum(ok.int(), 0) - 1
-            nb = base + L
-            lc = torch.where(ok, nb + 2 * rank, torch.full_like(rank, -1)).to(torch.int32)
-            rc = torch.where(ok, lc + 1, lc).to(torch.int32)
-            thr = torch.where(bb < edges.shape[1], edges[bf.long(), bb.clamp(max=edges.shape[1] - 1).long()],
-                              torch.full_like(best_gain, math.inf))
-            bflag = bf if cat_dev is None else bf | (cat_dev[bf.long()].to(torch.int32) * CAT_FLAG)
-            bflag = bflag | (bdl * DLEFT_FLAG)
-            feats.append(torch.where(ok, bflag, torch.full_like(bf, -1)))
-            thrs.append(torch.where(ok, thr, torch.full_like(thr, math.inf)))
-            lefts.append(lc)
-            rights.append(rc)
-            if n_split == 0:
-                break
-            imp.index_add_(0, bf[li].long(), best_gain[li].double())
-            n_leaves = n_leaves + n_split
-            # route every row one level down (leaves keep their id: split_feat < 0)
-            sf_all = torch.cat([sf_all, feats[-1]])
-            sb_all = torch.cat([sb_all, bb])
-            lc_all = torch.cat([lc_all, lc])
-            rc_all = torch.cat([rc_all, rc])
-            p = _native.ptr
-            rest = (p(node_of_row), p(sf_all), p(sb_all), p(lc_all), p(rc_all), (q.B - 1) if self.missing else -1)
-            if dev.type == "cuda":
-                src, cs = q.route_src()
-                _native.check(_native.hip().hm_route_rows(src, C.c_int64(n), q.dpad, C.c_int64(cs), base, base + L, *rest,
-                                                          int(node_of_row.dtype == torch.int16),
-                                                          _native.stream_of(dev)), "hm_route_rows")
-            else:
-                _native.host().hm_route_rows_cpu(p(q.bins), C.c_int64(n), q.dpad, *rest)
-            # next level: histogram the smaller child of every split, derive the sibling
-            left_tot = left_all[li]                                            # [S, NS]
-            right_tot = tot[li] - left_tot
-            small_right = self._weight(right_tot) < self._weight(left_tot)     # [S]
-            small_id = torch.where(small_right, rc[li], lc[li]) - nb           # local child id
-            lut = torch.full((2 * n_split,), 32767, dtype=torch.int16, device=dev)
-            lut[small_id.long()] = torch.arange(n_split, device=dev, dtype=torch.int16)
-            if dev.type == "cuda" and n_split <= 8192:
-                rows, seg = self._partition_gpu(act_rows, node_of_row, nb, lut, n_split)
-            else:
-                nr = node_of_row[act_rows.long()] - nb
-                key = torch.where(nr >= 0, lut[nr.clamp_min(0).long()], torch.full_like(nr, 32767, dtype=torch.int16))
-                skey, order = torch.sort(key, stable=True)
-                rows = act_rows[order].contiguous()
-                seg = torch.searchsorted(skey, torch.arange(n_split + 1, device=dev, dtype=torch.int16)).to(torch.int64)
-            Hs = self._hist(rows, seg.contiguous(), n_split, stats, smax)
-            Hn = torch.empty((2 * n_split, d, B, NS), dtype=torch.float32, device=dev)
-            if dev.type == "cuda":
-                sr8 = small_right.to(torch.uint8)
-                _native.check(_native.hip().hm_hist_sibling(
-                    _native.ptr(H), _native.ptr(Hs), _native.ptr(li), _native.ptr(sr8), C.c_int64(d * B * NS),
-                    n_split, _native.ptr(Hn), _native.stream_of(dev)), "hm_hist_sibling")
-            else:
-                sr = small_right.long()
-                j2 = 2 * torch.arange(n_split, device=dev)
-                Hn[j2 + sr] = Hs
-                Hn[j2 + 1 - sr] = H[li] - Hs
-            H = Hn
-            base, L = nb, 2 * n_split
-            depth += 1
-        defer = defer and fused
+            H = self._fused_level(s, H) if s.fused else self._tensor_level(s, H)
+        return self._finish_tree(s, leaf_h, defer)
+
+    def _finish_tree(self, s: "_TreeState", leaf_h, defer: bool):
+        """Newton leaf values (``leaf_h``), the builder's results, and the tree: materialised, or
+        left on the device as a :class:`PendingTree`."""
+        t, dev, node_of_row = s.nodes, s.stats.device, s.node_of_row
+        defer = defer and s.fused
         if defer:
-            self.imp_dev = imp
+            self.imp_dev = s.imp
         else:
-            self.importance = self.importance + imp.cpu().numpy()
+            self.importance = self.importance + s.imp.cpu().numpy()
         self.leaf_of_row = node_of_row
-        if fused and leaf_h is not None:
-            t = base + L
-            sums = torch.zeros((t, 2), dtype=torch.float32, device=dev)
-            p, st_ = _native.ptr, _native.stream_of(dev)
-            if t <= 8192:
-                _native.check(_native.hip().hm_leaf_sums(p(node_of_row), p(stats), p(leaf_h), C.c_int64(n), t,
-                                                         p(sums), int(node_of_row.dtype == torch.int16), st_),
-                              "hm_leaf_sums")
+        m = s.base + s.L                                   # nodes written, ids 0 .. m - 1
+        if s.fused and leaf_h is not None:
+            sums = torch.zeros((m, 2), dtype=torch.float32, device=dev)
+            p, st = _native.ptr, _native.stream_of(dev)
+            if m <= LEAF_SUMS_MAX_NODES:
+                _native.check(_native.hip().hm_leaf_sums(
+                    p(node_of_row), p(s.stats), p(leaf_h), C.c_int64(node_of_row.numel()), m, p(sums),
+                    int(node_of_row.dtype == torch.int16), st), "hm_leaf_sums")
             else:
                 ok = node_of_row >= 0
                 nd = node_of_row[ok].long()
-                sums[:, 0].index_add_(0, nd, stats[ok, 0])
+                sums[:, 0].index_add_(0, nd, s.stats[ok, 0])
                 sums[:, 1].index_add_(0, nd, leaf_h[ok])
             if self.mixer is not None and self.mixer.world > 1:
                 self.mixer.all_reduce_sum([sums])
-            _native.check(_native.hip().hm_leaf_newton(p(sums), p(nbuf.sf), t, p(nbuf.vals), st_), "hm_leaf_newton")
-        if fused:
-            t = base + L                                   # nodes written, ids 0 .. t - 1
-            self.node_values = nbuf.vals[:t]
-            if defer:
-                return PendingTree(nbuf.sf[:t], nbuf.thr[:t], nbuf.lc[:t], nbuf.rc[:t], nbuf.vals[:t], n_out)
-            F, Lc, Rc = torch.stack([nbuf.sf[:t], nbuf.lc[:t], nbuf.rc[:t]]).cpu().numpy()
-            T = nbuf.thr[:t].cpu().numpy()
-            V = self.node_values.double().cpu().numpy()
-        else:
-            F = torch.cat(feats).cpu().numpy()
-            T = torch.cat(thrs).cpu().numpy()
-            Lc = torch.cat(lefts).cpu().numpy()
-            Rc = torch.cat(rights).cpu().numpy()
-            V = torch.cat(vals).double().cpu().numpy()
-            self.node_values = torch.cat(vals)
-        return _tree_from_arrays(F, T, Lc, Rc, V, n_out)
+            _native.check(_native.hip().hm_leaf_newton(p(sums), p(t.sf), m, p(t.vals), st), "hm_leaf_newton")
+        self.node_values = t.vals[:m]
+        if defer:
+            return PendingTree(t.sf[:m], t.thr[:m], t.lc[:m], t.rc[:m], t.vals[:m], t.n_out)
+        F, Lc, Rc = torch.stack([t.sf[:m], t.lc[:m], t.rc[:m]]).cpu().numpy()
+        return _tree_from_arrays(F, t.thr[:m].cpu().numpy(), Lc, Rc, self.node_values.double().cpu().numpy(), t.n_out)
 
 
 def _tree_from_arrays(F, T, Lc, Rc, V, n_out: int) -> Tree:
@@ -1186,8 +1171,8 @@ class GradientTreeBoostingClassifier(Learner):
             # tree instead of ~12 tensor passes over the n rows (profiles/gbt_r2/)
             y1 = Y[:, 0].contiguous()
             # gbt2: the histograms carry (r, w) and the Newton leaf values sum h per leaf afterwards
-            # (2 LDS statistics instead of 3); HM_GBT2=0 keeps (r, h, w) histograms
-            gbt2 = GBT2 and c["max_leaf_nodes"] is None      # (the level-fused builder only)
+            # (2 LDS statistics instead of 3); -max_leaf_nodes keeps (r, h, w) histograms
+            gbt2 = c["max_leaf_nodes"] is None               # (the level-fused builder only)
             ns = 2 if gbt2 else 3
             stats_buf = torch.empty((n, ns), dtype=torch.float32, device=self.device)
             hh = torch.empty(n, dtype=torch.float32, device=self.device) if gbt2 else None

@@ -1070,14 +1070,19 @@ def _compaction(sf, lc, rc):
     return remap
 
 
-def _grow(monkeypatch, q, kind, stats, heap, route_fused, last_splits, identity=False, max_leaves=None, active=None):
+def _grow(monkeypatch, q, kind, stats, heap, route_fused, last_splits, identity=False, max_leaves=None, active=None,
+          leaf_h=None, builder=None):
+    """(tree, leaf of every row in the tree's numbering, importance) of one build under the given
+    switches; ``builder``: a list that receives the HistTreeBuilder."""
     monkeypatch.setattr(T, "HEAP_TREES", heap)
     monkeypatch.setattr(T, "ROUTE_FUSED", route_fused)
     monkeypatch.setattr(T, "LAST_FROM_SPLITS", last_splits)
     n = stats.shape[0]
     b = HistTreeBuilder(q, kind, max_depth=6, min_samples_split=500, max_leaf_nodes=max_leaves, seed=1)
+    if builder is not None:
+        builder.append(b)
     kw = dict(act_rows=torch.arange(n, dtype=torch.int32, device="cuda"), identity_rows=True) if identity else {}
-    out = b.build(stats, active=active, defer=True, **kw)
+    out = b.build(stats, active=active, defer=True, leaf_h=leaf_h, **kw)
     raw = b.leaf_of_row.long().cpu().numpy()
     if isinstance(out, T.PendingTree):
         sf, _, lc, rc, _ = (a.cpu().numpy() for a in out.arrays)
@@ -1134,3 +1139,91 @@ def test_every_gpu_build_path_grows_the_same_tree(monkeypatch, kind, missing):
         for last_splits in (False, True):
             got = _grow(monkeypatch, q, kind, stats, heap, True, last_splits, active=active.cuda())
             _same_tree(got, abase, f"heap={heap} last={last_splits} active mask")
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["gini", "variance"])
+def test_sort_fallback_grows_the_same_tree_on_gpu(monkeypatch, kind):
+    """Levels with more keys than the counting-sort partition takes group the small children's
+    rows by a stable sort.  With the limit patched to 2 every level from depth 2 on takes it, in
+    both fused layouts (the heap level has L = 2^depth keys, the compact one its split count; with
+    identity rows the fused route + count pass is bounded alike) and in the tensor loop on CUDA;
+    each must grow the tree of the unpatched tensor loop."""
+    n = 20000
+    X, stats = _exact_tree_data(kind, n, seed=0)
+    q = quantize(X.cuda(), 64, missing=True)
+    stats = stats.cuda()
+    base = _grow(monkeypatch, q, kind, stats, True, True, True, max_leaves=64)
+    assert base[0].depth() == 6 and len(base[0].feature) > 30
+    monkeypatch.setattr(T, "PARTITION_MAX_KEYS", 2)
+    counted = []
+    part, route_part = HistTreeBuilder._partition_gpu, HistTreeBuilder._route_partition_gpu
+
+    def spy_part(act_rows, node_of_row, nb, lut, n_keys):
+        counted.append(n_keys)
+        return part(act_rows, node_of_row, nb, lut, n_keys)
+
+    def spy_route_part(self, n_, node_of_row, nbuf, nb, lut, n_keys, lo):
+        counted.append(n_keys)
+        return route_part(self, n_, node_of_row, nbuf, nb, lut, n_keys, lo)
+
+    monkeypatch.setattr(HistTreeBuilder, "_partition_gpu", staticmethod(spy_part))
+    monkeypatch.setattr(HistTreeBuilder, "_route_partition_gpu", spy_route_part)
+    # splitting nodes per level of the tree; the fused layouts group the children of levels 0 .. 4
+    # (the last level's come from the split search), the tensor loop those of level 5 too
+    splits, level = [], [0]
+    while level:
+        level = [k for k in level if base[0].feature[k] >= 0]
+        splits.append(len(level))
+        level = [c for k in level for c in (base[0].left[k], base[0].right[k])]
+    assert max(splits[:5]) > 2
+    configs = [("heap", dict(heap=True), [1, 2]),
+               ("compact", dict(heap=False), [s for s in splits[:5] if 0 < s <= 2]),
+               ("max_leaves", dict(heap=True, max_leaves=64), [s for s in splits[:6] if 0 < s <= 2])]
+    for name, kw, within in configs:
+        for identity in (False, True):
+            del counted[:]
+            got = _grow(monkeypatch, q, kind, stats, route_fused=True, last_splits=True, identity=identity, **kw)
+            _same_tree(got, base, f"{name} identity={identity}")
+            # only the levels within the limit reached the counting sort: the others were sorted
+            assert counted == within, (name, identity, counted)
+
+
+@gpu
+@pytest.mark.parametrize("identity", [False, True])
+def test_leaf_h_newton_leaves_in_both_fused_layouts(monkeypatch, identity):
+    """criterion gbt2 on (w y, w) with per-row hessians k / 64: the leaves of a deferred tree hold
+    fl32(sum r) / fl32(sum h) over their rows (leaf_newton_kernel's rule; both sums are exact in
+    fp32: integers below 2^24 / 64), in the heap and the compact layout, with the last level's
+    records from the split search or from histograms; all four materialise the same tree."""
+    n = 20000
+    X, stats = _exact_tree_data("variance", n, seed=0)
+    q = quantize(X.cuda(), 64, missing=True)
+    k = torch.randint(1, 65, (n,), generator=torch.Generator().manual_seed(11))
+    leaf_h = k.float() / 64
+    r64, h64 = stats[:, 0].double().numpy(), leaf_h.double().numpy()
+    stats, leaf_h = stats.cuda(), leaf_h.cuda()
+    first = None
+    for heap in (True, False):
+        for last_splits in (False, True):
+            tag = f"heap={heap} last={last_splits}"
+            bs = []
+            got = _grow(monkeypatch, q, "gbt2", stats, heap, True, last_splits, identity=identity, leaf_h=leaf_h,
+                        builder=bs)
+            b = bs[0]
+            assert (b.leaf_of_row.dtype == torch.int16) == heap, tag
+            raw = b.leaf_of_row.long().cpu().numpy()
+            assert (raw >= 0).all()
+            vals = b.node_values.cpu().numpy()
+            assert vals.shape[1] == 1
+            leaves = np.unique(raw)
+            assert len(leaves) > 16, tag
+            sum_r = np.bincount(raw, weights=r64, minlength=len(vals))
+            sum_h = np.bincount(raw, weights=h64, minlength=len(vals))
+            want = np.float32(sum_r[leaves]) / np.float32(sum_h[leaves])
+            np.testing.assert_array_equal(vals[leaves, 0], want, err_msg=tag)
+            assert got[0].depth() == 6, tag
+            if first is None:
+                first = got
+            else:
+                _same_tree(got, first, tag)
