@@ -25,7 +25,10 @@ _CF_OPTS = Options([
     opt("changepoint_threshold", None, -1.0, float, "Change-point threshold"),
     opt("loss_function", None, "hellinger", str, "hellinger | logloss"),
     opt("loss_function1", None, None, str, "Loss of stage 1"),
-    opt("loss_function2", None, None, str, "Loss of stage 2")], "changefinder")
+    opt("loss_function2", None, None, str, "Loss of stage 2"),
+    opt("engine", None, "auto", str, "auto | native | python: native = the time-parallel SDAR scan "
+        "engine (ops/changefinder.py); auto = native on a cuda session for options inside its "
+        "limits and a finite rectangular input, python otherwise")], "changefinder")
 
 
 class SDAR1D:
@@ -119,12 +122,75 @@ class ChangeFinder:
         return out
 
 
+def _cf_rectangular(xs):
+    """The input as fp64 [N, D] if it is all scalars or all vectors of one length, else None."""
+    try:
+        rows = [np.asarray(x, dtype=np.float64) for x in xs]
+    except (TypeError, ValueError):
+        return None
+    if not rows or any(r.ndim != rows[0].ndim or r.shape != rows[0].shape for r in rows):
+        return None
+    if rows[0].ndim > 1:
+        return None
+    return np.stack(rows).reshape(len(rows), -1)
+
+
+def _cf_native(x: np.ndarray, c, l1, l2, device):
+    """The rows of ``changefinder`` from ``ops.changefinder.changefinder_scores`` on ``device``."""
+    import torch
+
+    from ..ops import changefinder as ops_cf
+
+    try:
+        o, cp = ops_cf.changefinder_scores(torch.from_numpy(x[None]).to(device), c["k"], c["r1"],
+                                           c["r2"], c["T1"], c["T2"], l1, l2)
+    except ValueError as ex:
+        raise UDFArgumentException(str(ex)) from None
+    ot, ct = c["outlier_threshold"], c["changepoint_threshold"]
+    rows = zip(o[0].cpu().tolist(), cp[0].cpu().tolist())
+    if ot >= 0 or ct >= 0:
+        return [[a, b, a > ot >= 0, b > ct >= 0] for a, b in rows]
+    return [[a, b] for a, b in rows]
+
+
 @udf("changefinder", vectorized=True)
-def changefinder(xs, options=None):
-    """Per ordered input: [outlier_score, changepoint_score(, is_outlier, is_changepoint)]."""
+def changefinder(xs, options=None, session=None):
+    """Per ordered input: [outlier_score, changepoint_score(, is_outlier, is_changepoint)].
+    `-engine native` runs the time-parallel SDAR scan engine (ops/changefinder.py: the gfx950
+    kernels on a cuda device, the OpenMP twin on the CPU); `-engine auto` (default) picks it on a
+    cuda session when the options are inside its limits (k <= 32, T1, T2 <= 1024) and the input is
+    finite and rectangular, and the per-point Python loop otherwise."""
     o = options[0] if isinstance(options, (list, tuple, np.ndarray)) else options
     cf = ChangeFinder(o)
+    engine = cf.c["engine"]
+    if engine not in ("auto", "native", "python"):
+        raise UDFArgumentException(f"changefinder: -engine must be auto, native or python, got {engine!r}")
+    if engine != "python":
+        from ..models.base import resolve_device
+
+        dev = None if session is None or session.device is None else resolve_device(session.device)
+        if engine == "native" or (dev is not None and dev.type == "cuda"):
+            from ..ops.changefinder import supports
+
+            xs = list(xs)
+            x = _cf_rectangular(xs)
+            c = cf.c
+            if engine == "native":
+                if not xs:
+                    return []
+                if x is None:
+                    raise UDFArgumentException("changefinder: -engine native needs all scalars or all "
+                                               "vectors of one length")
+                return _cf_native(x, c, cf.l1, cf.l2, dev or resolve_device(None))
+            # auto: the native engine on a cuda session, for options inside its limits and a finite
+            # rectangular input; everything else runs below as it always did
+            if (x is not None and x.size and bool(np.isfinite(x).all())
+                    and supports(c["k"], c["r1"], c["r2"], c["T1"], c["T2"], cf.l1, cf.l2)):
+                return _cf_native(x, c, cf.l1, cf.l2, dev)
     return [cf.step(x) for x in xs]
+
+
+changefinder.wants_session = True
 
 
 _SST_OPTS = Options([
