@@ -53,19 +53,122 @@ class HyperLogLog:
         return int(round(e))
 
 
-@udaf("approx_count_distinct")
-def approx_count_distinct(values, options=None):
-    p = 15
+def _acd_options(options) -> tuple:
+    """``(p, engine)`` of the option string ``[-p N] [-engine auto|native|python]``."""
+    p, engine = 15, "auto"
     o = options[0] if isinstance(options, (list, tuple)) and options else options
     if o:
         toks = str(o).split()
         if "-p" in toks:
             p = int(toks[toks.index("-p") + 1])
+        if "-engine" in toks:
+            engine = toks[toks.index("-engine") + 1]
+            if engine not in ("auto", "native", "python"):
+                raise ValueError(f"approx_count_distinct: -engine must be auto, native or python, got {engine!r}")
+    return p, engine
+
+
+@udaf("approx_count_distinct")
+def approx_count_distinct(values, options=None):
+    p, engine = _acd_options(options)
+    if engine == "native":
+        values = list(values) if not hasattr(values, "__len__") else values
+        return approx_count_distinct_grouped(values, np.zeros(len(values), dtype=np.int32), 1, p)[0]
     h = HyperLogLog(p)
     for v in values:
         if v is not None:
             h.add(v)
     return h.cardinality()
+
+
+# ---- the native engine (ops/sketch.py): whole columns, every group in one pass.  Contract as
+# the classes above: h64 = (mm3(s, 0x9747B28C) << 32) | mm3(s, 0x5BD1E995), idx = h64 >> (64 - p),
+# rho = min(clz64(h64 << p), 64 - p) + 1, reg = max(reg, rho); the estimate is computed on the
+# host from the register histogram and equals cardinality() while p + max(reg) <= 53 (it may
+# differ by 1 beyond).  Bloom: h1 = mm3(s, 0), h2 = mm3(s, h1), bits (h1 + j * h2) mod m.
+_NATIVE_MAX_BYTES = 1 << 30          # G * 2^p registers the auto engine will allocate
+_BLOOM_TEST_MAX_BYTES = 64 << 20     # F * m / 8 filter bytes the batch forms will stage
+
+
+def _sketch_device(device):
+    from ..models.base import resolve_device
+
+    return resolve_device(device)
+
+
+def _packed_groups(values, gid, G: int):
+    """``(buf, off, gid int32)`` CPU tensors of the non-NULL values, or None when the column does
+    not pack (``ops.sketch.pack_value_column``)."""
+    import torch
+
+    from ..ops import sketch as sk
+
+    packed = sk.pack_value_column(values)
+    if packed is None:
+        return None
+    buf, off, keep = packed
+    g = np.asarray(gid)
+    n = len(values)
+    if g.ndim != 1 or len(g) != n:
+        raise ValueError(f"sketch: gid must hold one group per value ({n}), got shape {g.shape}")
+    g = g[keep.numpy()]
+    if len(g) and (int(g.min()) < 0 or int(g.max()) >= G):
+        raise ValueError(f"sketch: gid must be in 0..{G - 1}")
+    return buf, off, torch.from_numpy(np.ascontiguousarray(g, dtype=np.int32))
+
+
+def _acd_native(values, gid, G: int, p: int, device, strict: bool):
+    from ..ops import sketch as sk
+
+    G, p = int(G), int(p)
+    if not (sk.P_MIN <= p <= sk.P_MAX) or G < 1 or (G << p) > _NATIVE_MAX_BYTES:
+        if strict:
+            raise ValueError(f"approx_count_distinct: the native engine takes p in {sk.P_MIN}..{sk.P_MAX} "
+                             f"and G * 2^p <= {_NATIVE_MAX_BYTES}, got p = {p}, G = {G}")
+        return None
+    packed = _packed_groups(values, gid, G)
+    if packed is None:
+        if strict:
+            raise ValueError("approx_count_distinct: the native engine takes a column of str or of "
+                             "integers")
+        return None
+    dev = _sketch_device(device)
+    reg = sk.hll_registers(*(t.to(dev) for t in packed), G, p, check=False)      # packed here
+    return sk.hll_estimate(sk.hll_histogram(reg), p)
+
+
+def approx_count_distinct_grouped(values, gid, G: int, p: int = 15, device=None) -> list:
+    """``[approx_count_distinct(values of group g, f"-p {p}") for g in range(G)]`` in one native
+    pass: ``values`` is a column of ``str`` or of integers (NULLs are skipped), ``gid`` the group of
+    every value.  Runs on ``device`` (default: the GPU when there is one)."""
+    return _acd_native(values, gid, G, p, device, strict=True)
+
+
+def _acd_grouped(values, options=None, *, codes, n_groups, session=None):
+    """The column-at-once form the SQL executor calls (``registry``): None -> the per-group loop."""
+    if options is None:
+        p, engine = 15, "auto"
+    else:
+        try:
+            ops = set(options.tolist() if hasattr(options, "tolist") else options)
+        except TypeError:
+            return None
+        if len(ops) != 1:                              # not one constant (or no rows at all)
+            return None
+        p, engine = _acd_options(ops.pop())
+    if engine == "python":
+        return None
+    return _acd_native(values, codes, n_groups, p, None if session is None else session.device,
+                       strict=engine == "native")
+
+
+def _grouped_adapter(fn):
+    def grouped(arg_series, codes, n_groups, session=None):
+        return fn(*arg_series, codes=codes, n_groups=n_groups, session=session)
+    return grouped
+
+
+approx_count_distinct.grouped = _grouped_adapter(_acd_grouped)
 
 
 # ------------------------------------------------------------------ Bloom filters
@@ -105,6 +208,41 @@ def bloom(values):
     return b.serialize()
 
 
+def _bloom_serialize(m: int, k: int, bits) -> list:
+    return [f"{m}:{k}:" + base64.b64encode(row.tobytes()).decode() for row in bits.cpu().numpy()]
+
+
+def _bloom_native(values, gid, G: int, device, strict: bool):
+    from ..ops import sketch as sk
+
+    G = int(G)
+    m, k = 1 << 16, 4                                  # Bloom()'s defaults, as bloom() uses them
+    if G < 1 or G * (m // 8) > _NATIVE_MAX_BYTES:
+        if strict:
+            raise ValueError(f"bloom: the native engine takes 1..{_NATIVE_MAX_BYTES // (m // 8)} groups")
+        return None
+    packed = _packed_groups(values, gid, G)
+    if packed is None:
+        if strict:
+            raise ValueError("bloom: the native engine takes a column of str or of integers")
+        return None
+    dev = _sketch_device(device)
+    return _bloom_serialize(m, k, sk.bloom_bits(*(t.to(dev) for t in packed), G, m, k, check=False))
+
+
+def bloom_grouped(values, gid, G: int, device=None) -> list:
+    """``[bloom(values of group g) for g in range(G)]`` (the ``m:k:base64`` strings) in one native
+    pass; see ``approx_count_distinct_grouped``."""
+    return _bloom_native(values, gid, G, device, strict=True)
+
+
+def _bloom_grouped_sql(values, *, codes, n_groups, session=None):
+    return _bloom_native(values, codes, n_groups, None if session is None else session.device, strict=False)
+
+
+bloom.grouped = _grouped_adapter(_bloom_grouped_sql)
+
+
 @udf("bloom_and")
 def bloom_and(a, b):
     A, B = Bloom.deserialize(a), Bloom.deserialize(b)
@@ -132,6 +270,125 @@ def bloom_contains(a, key):
 def bloom_contains_any(a, keys):
     B = Bloom.deserialize(a)
     return any(B.contains(k) for k in keys)
+
+
+def _bloom_filter_arg(a, n: int):
+    """``(bits uint8 [F, m / 8], fid int32 [n], null bool [n], k)`` for the filter argument of a
+    batch call - a constant string or a column, factorised to its distinct strings - or None
+    when it is anything else, a filter does not parse, the filters differ in ``(m, k)`` or are
+    larger than ``_BLOOM_TEST_MAX_BYTES`` together."""
+    import pandas as pd
+
+    if isinstance(a, pd.Series):
+        vals = a.tolist()
+        if len(vals) != n:
+            return None
+    elif isinstance(a, str):
+        vals = [a] * n if n else []
+    else:
+        return None
+    ids: dict = {}
+    fid = np.zeros(n, dtype=np.int32)
+    null = np.zeros(n, dtype=bool)
+    last, last_id = None, 0
+    for r, v in enumerate(vals):
+        if v is None:
+            null[r] = True
+        elif v is last:                                # a constant repeats one object
+            fid[r] = last_id
+        elif isinstance(v, str):
+            last, last_id = v, ids.setdefault(v, len(ids))
+            fid[r] = last_id
+        else:
+            return None
+    if not ids:
+        return None
+    rows, mk = [], None
+    for s in ids:                                      # insertion order = id order
+        try:
+            m, k, b = s.split(":", 2)
+            m, k = int(m), int(k)
+            bits = np.frombuffer(base64.b64decode(b), dtype=np.uint8)
+        except ValueError:
+            return None
+        if not (32 <= m <= 1 << 26) or m % 32 or not 1 <= k <= 16 or len(bits) != m // 8:
+            return None
+        if mk is None:
+            mk = (m, k)
+        elif mk != (m, k):
+            return None
+        if (len(rows) + 1) * (m // 8) > _BLOOM_TEST_MAX_BYTES:
+            return None
+        rows.append(bits)
+    return np.stack(rows), fid, null, mk[1]
+
+
+def _bloom_hits(flt, fid, packed, session):
+    import torch
+
+    from ..ops import sketch as sk
+
+    dev = _sketch_device(None if session is None else session.device)
+    bits, k = torch.from_numpy(flt[0]).to(dev), flt[3]
+    buf, off, _ = packed
+    return sk.bloom_test(bits, torch.from_numpy(fid).to(dev), buf.to(dev), off.to(dev), k,
+                         check=False).cpu().numpy().astype(bool)
+
+
+def _bloom_result(hit, null):
+    import pandas as pd
+
+    vals = [None if z else bool(h) for h, z in zip(hit, null)]
+    return pd.Series(vals, dtype=object).infer_objects() if vals else pd.Series([], dtype=object)
+
+
+def _bloom_contains_batch(a, key, session=None):
+    """Column-at-once ``bloom_contains``: a Series, or None (-> the per-row path and whatever it
+    raises) unless the keys are a column of str or integers without NULLs and every filter parses
+    (``_bloom_filter_arg``).  A NULL filter row stays NULL."""
+    import pandas as pd
+
+    from ..ops import sketch as sk
+
+    if not isinstance(key, pd.Series):
+        return None
+    n = len(key)
+    flt = _bloom_filter_arg(a, n)
+    packed = sk.pack_value_column(key) if flt is not None else None
+    if packed is None or packed[2].numel() != n:
+        return None
+    return _bloom_result(_bloom_hits(flt, flt[1], packed, session), flt[2])
+
+
+def _bloom_contains_any_batch(a, keys, session=None):
+    """Column-at-once ``bloom_contains_any``: the keys are a list column, tested key by key and
+    reduced per row with an any; see ``_bloom_contains_batch``."""
+    import pandas as pd
+
+    from ..ops import sketch as sk
+
+    if not isinstance(keys, pd.Series):
+        return None
+    rows = keys.tolist()
+    n = len(rows)
+    flt = _bloom_filter_arg(a, n)
+    if flt is None:
+        return None
+    for r in rows:
+        if not isinstance(r, (list, tuple, np.ndarray)):
+            return None
+    lens = np.fromiter((len(r) for r in rows), dtype=np.int64, count=n)
+    flat = [k for r in rows for k in (r.tolist() if isinstance(r, np.ndarray) else r)]
+    packed = sk.pack_value_column(flat)
+    if packed is None or packed[2].numel() != len(flat):
+        return None
+    row_of = np.repeat(np.arange(n, dtype=np.int64), lens)
+    hit = _bloom_hits(flt, np.ascontiguousarray(flt[1][row_of]), packed, session)
+    return _bloom_result(np.bincount(row_of[hit], minlength=n) > 0, flt[2])
+
+
+bloom_contains.batch = _bloom_contains_batch
+bloom_contains_any.batch = _bloom_contains_any_batch
 
 
 # ------------------------------------------------------------------ geospatial (slippy tiles)

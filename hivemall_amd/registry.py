@@ -6,7 +6,13 @@ registered with a decorator that records its SQL kind:
 
 * ``udf``   scalar, called per row (``impl(*args)``) or vectorised (``impl(*columns)``);
 * ``udaf``  aggregate, called once per group with the group's argument columns as lists
-            (``impl(*columns) -> value``);
+            (``impl(*columns) -> value``).  An aggregate may also carry a column-at-once form,
+            ``impl.grouped(arg_series, codes, n_groups, session=...)``: the argument columns as
+            pandas Series, the group ``0..n_groups-1`` of every row (unsorted) and the number of
+            groups in, a sequence of ``n_groups`` values out, or None to decline the input.  The
+            SQL executor tries it before the per-group loop (``Session._agg_grouped``; not for
+            ``DISTINCT``, not with ``HM_SQL_BATCH_UDTF=0``) and falls back to the loop on None;
+            ``approx_count_distinct`` and ``bloom`` have one (``ops/sketch.py``);
 * ``udtf``  table function.  ``per_row=True``: ``impl(*args) -> iterable of tuples`` per input
             row (explode-like, usable in ``LATERAL VIEW``).  ``per_row=False``: called once with
             every input row's arguments (``impl(*columns) -> DataFrame``) — the learners.

@@ -1208,6 +1208,9 @@ class Session:
         impl = fd.impl if fd is not None else B.AGGREGATE.get(name)
         if impl is None:
             raise SQLError(f"unknown aggregate function {name}")
+        res = self._agg_grouped(impl, a.distinct, arg_vals, codes, n_groups)
+        if res is not None:
+            return pd.Series(res, dtype=object)
         lists = [v.tolist() for v in arg_vals]
         out = []
         for g in range(n_groups):
@@ -1224,6 +1227,22 @@ class Session:
                 cols = [[c[r] for r in keep] for c in cols]
             out.append(impl(*cols))
         return pd.Series(out, dtype=object)
+
+    def _agg_grouped(self, impl, distinct: bool, arg_series: list, codes, n_groups: int):
+        """Column-at-once form of an aggregate that opts in (``impl.grouped``, see the registry's
+        module docstring): the argument columns, the group of every row and the number of
+        groups in, one value per group out.  None -> the per-group loop: no such form, DISTINCT,
+        ``HM_SQL_BATCH_UDTF=0``, or the form declined this input."""
+        grouped = getattr(impl, "grouped", None)
+        if grouped is None or distinct or n_groups < 1 or os.environ.get("HM_SQL_BATCH_UDTF", "1") == "0":
+            return None
+        res = grouped(arg_series, codes, n_groups, session=self)
+        if res is None:
+            return None
+        res = list(res)
+        if len(res) != n_groups:
+            raise SQLError(f"grouped aggregate returned {len(res)} values for {n_groups} groups")
+        return res
 
     # -- windows
     def _window(self, f: Func, src: Frame, ctes) -> pd.Series:
@@ -1520,8 +1539,11 @@ class Session:
             impl = fd.impl if fd is not None else B.AGGREGATE[name]
             if name == "count" and (f.star or not f.args):
                 return n
-            cols = [_ser(self.eval(a, fr, ctes, vals), n).tolist() for a in f.args]
-            return impl(*cols)
+            cols = [_ser(self.eval(a, fr, ctes, vals), n) for a in f.args]
+            res = self._agg_grouped(impl, f.distinct, cols, np.zeros(n, dtype=np.int64), 1)
+            if res is not None:
+                return res[0]
+            return impl(*[c.tolist() for c in cols])
         if name == "rand":
             return B._rand(None if not f.args else _ser(self.eval(f.args[0], fr, ctes, vals), n), n)
         args = [self.eval(a, fr, ctes, vals) for a in f.args]
