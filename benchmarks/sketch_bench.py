@@ -142,7 +142,7 @@ def main():
     import torch
 
     from hivemall_amd import misc
-    from hivemall_amd.ops import sketch as sk
+    from hivemall_amd.ops import _args, sketch as sk
 
     if not a.cpu_only and not torch.cuda.is_available():
         raise SystemExit("sketch_bench: no GPU")
@@ -160,7 +160,7 @@ def main():
     if not a.cpu_only:
         dev = torch.device("cuda")
         sync = lambda: torch.cuda.synchronize(dev)          # noqa: E731
-        buf, off = sk._pad16(buf_h.to(dev)), off_h.to(dev)
+        buf, off = _args.pad16(buf_h.to(dev)), off_h.to(dev)
         for G, p in HLL_ROWS:
             gid = gids_h[G].to(dev)
             gid64 = gid.long()

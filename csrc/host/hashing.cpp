@@ -17,39 +17,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../kernels/murmur3.h"
+
 #define HM_API extern "C" __attribute__((visibility("default")))
 
 namespace {
 
-inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-uint32_t murmur3_x86_32(const uint8_t* data, int len, uint32_t seed) {
-    const int nblocks = len / 4;
-    uint32_t h1 = seed;
-    const uint32_t c1 = 0xcc9e2d51u, c2 = 0x1b873593u;
-    for (int i = 0; i < nblocks; ++i) {
-        uint32_t k1;
-        std::memcpy(&k1, data + 4 * i, 4);  // little-endian host
-        k1 *= c1; k1 = rotl32(k1, 15); k1 *= c2;
-        h1 ^= k1; h1 = rotl32(h1, 13); h1 = h1 * 5 + 0xe6546b64u;
-    }
-    const uint8_t* tail = data + nblocks * 4;
-    uint32_t k1 = 0;
-    switch (len & 3) {
-        case 3: k1 ^= (uint32_t)tail[2] << 16; [[fallthrough]];
-        case 2: k1 ^= (uint32_t)tail[1] << 8; [[fallthrough]];
-        case 1: k1 ^= tail[0]; k1 *= c1; k1 = rotl32(k1, 15); k1 *= c2; h1 ^= k1;
-    }
-    h1 ^= (uint32_t)len;
-    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu; h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u; h1 ^= h1 >> 16;
-    return h1;
-}
-
-inline int32_t mhash_reduce(uint32_t h, int32_t num_features) {
-    int32_t r = (int32_t)h % num_features;  // Java int % semantics
-    if (r < 0) r += num_features;
-    return r + 1;
-}
+using hm::mhash_reduce;
+using hm::murmur3_bytes;
 
 // Strict integer parse of [p, p+n) ; returns false if not an integer literal.
 bool parse_int(const char* p, int n, int64_t* out) {
@@ -126,21 +101,21 @@ struct Dict {
 }  // namespace
 
 HM_API uint32_t hm_murmur3(const uint8_t* data, int len, uint32_t seed) {
-    return murmur3_x86_32(data, len, seed);
+    return murmur3_bytes(data, len, seed);
 }
 
 HM_API void hm_murmur3_batch(const uint8_t* buf, const int64_t* off, int64_t n, uint32_t seed,
                              uint32_t* out) {
 #pragma omp parallel for schedule(static) if (n > 65536)
     for (int64_t i = 0; i < n; ++i)
-        out[i] = murmur3_x86_32(buf + off[i], (int)(off[i + 1] - off[i]), seed);
+        out[i] = murmur3_bytes(buf + off[i], (int)(off[i + 1] - off[i]), seed);
 }
 
 HM_API void hm_mhash_batch(const uint8_t* buf, const int64_t* off, int64_t n, uint32_t seed,
                            int32_t num_features, int32_t* out) {
 #pragma omp parallel for schedule(static) if (n > 65536)
     for (int64_t i = 0; i < n; ++i)
-        out[i] = mhash_reduce(murmur3_x86_32(buf + off[i], (int)(off[i + 1] - off[i]), seed),
+        out[i] = mhash_reduce(murmur3_bytes(buf + off[i], (int)(off[i + 1] - off[i]), seed),
                               num_features);
 }
 
@@ -215,7 +190,7 @@ HM_API int64_t hm_feature_hash_strs(const uint8_t* buf, const int64_t* off, int6
         const int L = (int)(off[i + 1] - off[i]);
         bool hv;
         const int nl = feature_name_len(p, L, &hv);
-        const int32_t h = mhash_reduce(murmur3_x86_32(p, nl, seed), num_features);   // >= 1
+        const int32_t h = mhash_reduce(murmur3_bytes(p, nl, seed), num_features);   // >= 1
         out_off[i + 1] = dec_digits((uint32_t)h) + (hv ? L - nl : 0);
     }
     prefix_sum_inplace(out_off, n);
@@ -226,7 +201,7 @@ HM_API int64_t hm_feature_hash_strs(const uint8_t* buf, const int64_t* off, int6
         bool hv;
         const int nl = feature_name_len(p, L, &hv);
         uint8_t* o = out + out_off[i];
-        const int hd = fmt_i32(mhash_reduce(murmur3_x86_32(p, nl, seed), num_features),
+        const int hd = fmt_i32(mhash_reduce(murmur3_bytes(p, nl, seed), num_features),
                                reinterpret_cast<char*>(o));
         if (hv) {
             o[hd] = ':';
@@ -317,7 +292,7 @@ HM_API int64_t hm_parse_features(const uint8_t* buf, const int64_t* off, int64_t
             if (mode == 0) {
                 if (!parse_int(s, nlen, &id)) { bad = i < bad ? i : bad; continue; }
             } else {
-                id = mhash_reduce(murmur3_x86_32((const uint8_t*)s, nlen, seed), num_features);
+                id = mhash_reduce(murmur3_bytes((const uint8_t*)s, nlen, seed), num_features);
             }
             idx_out[i] = id;
             val_out[i] = v;
@@ -344,7 +319,7 @@ HM_API int64_t hm_parse_features(const uint8_t* buf, const int64_t* off, int64_t
                 id = D->encode(std::string_view(s, (size_t)nlen), add_new != 0);
                 break;
             case 2:
-                id = mhash_reduce(murmur3_x86_32((const uint8_t*)s, nlen, seed), num_features);
+                id = mhash_reduce(murmur3_bytes((const uint8_t*)s, nlen, seed), num_features);
                 break;
             default:
                 if (!parse_int(s, nlen, &id)) {
@@ -379,7 +354,7 @@ HM_API int64_t hm_parse_ffm_features(const uint8_t* buf, const int64_t* off, int
         int64_t f, id;
         if (!parse_int(s, flen, &f)) {
             if (flen <= 0) return i;
-            f = mhash_reduce(murmur3_x86_32((const uint8_t*)s, flen, seed), num_fields) - 1;
+            f = mhash_reduce(murmur3_bytes((const uint8_t*)s, flen, seed), num_fields) - 1;
         }
         if (f < 0 || f >= num_fields) return i;
         if (ilen <= 0) return i;
@@ -391,7 +366,7 @@ HM_API int64_t hm_parse_ffm_features(const uint8_t* buf, const int64_t* off, int
                 return i;
             }
         } else {
-            id = mhash_reduce(murmur3_x86_32((const uint8_t*)rest, ilen, seed), num_features) - 1;
+            id = mhash_reduce(murmur3_bytes((const uint8_t*)rest, ilen, seed), num_features) - 1;
         }
         fld_out[i] = (int32_t)f;
         idx_out[i] = (int32_t)id;

@@ -12,19 +12,11 @@
 #include <cstring>
 #include <vector>
 
+#include "../kernels/murmur3.h"
+
 #define HM_API extern "C" __attribute__((visibility("default")))
 
 namespace {
-
-constexpr uint32_t C1 = 0xcc9e2d51u, C2 = 0x1b873593u;
-
-inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-inline uint32_t premix(uint32_t k1) {
-    k1 *= C1;
-    k1 = rotl32(k1, 15);
-    return k1 * C2;
-}
 
 // [+-]digits[.digits][e[+-]digits] as strtod reads it: the forms Python's float() and strtod
 // agree on.  Spaces, underscores, inf / nan words, hex and texts over 63 bytes are not plain.
@@ -90,16 +82,9 @@ HM_API int hm_minhash_sig_cpu(const uint8_t* buf, const int64_t* off, const int3
                 for (int i = 0; i < nw; ++i) {
                     uint32_t k1;
                     std::memcpy(&k1, p + 4 * i, 4);   // little-endian host
-                    words.push_back(premix(k1));
+                    words.push_back(hm::mm_premix(k1));
                 }
-                const uint8_t* tp = p + 4 * nw;
-                uint32_t k1 = 0;
-                switch (L & 3) {
-                    case 3: k1 ^= (uint32_t)tp[2] << 16; [[fallthrough]];
-                    case 2: k1 ^= (uint32_t)tp[1] << 8; [[fallthrough]];
-                    case 1: k1 ^= tp[0];
-                }
-                tail.push_back(premix(k1));           // premix(0) == 0: no tail, no change
+                tail.push_back(hm::mm_premix(hm::mm_tail_word(p + 4 * nw, L & 3)));   // 0 when no tail
                 len.push_back((uint32_t)L);
                 wbeg.push_back((int64_t)words.size());
             }
@@ -109,14 +94,8 @@ HM_API int hm_minhash_sig_cpu(const uint8_t* buf, const int64_t* off, const int3
                 uint32_t m = 0xFFFFFFFFu;
                 for (int64_t j = 0; j < nf; ++j) {
                     uint32_t h1 = seed;
-                    for (int64_t i = wbeg[j]; i < wbeg[j + 1]; ++i) {
-                        h1 ^= words[i];
-                        h1 = rotl32(h1, 13);
-                        h1 = h1 * 5 + 0xe6546b64u;
-                    }
-                    h1 ^= tail[j];
-                    h1 ^= len[j];
-                    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu; h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u; h1 ^= h1 >> 16;
+                    for (int64_t i = wbeg[j]; i < wbeg[j + 1]; ++i) h1 = hm::mm_chain(h1, words[i]);
+                    h1 = hm::mm_fmix(h1 ^ tail[j], len[j]);
                     m = h1 < m ? h1 : m;
                 }
                 o[h] = m;

@@ -2,7 +2,7 @@
 // hm_bloom_test): the same contract, OpenMP over the values.
 //
 // Contract.  mm3 = MurmurHash3_x86_32 over the UTF-8 bytes of a value, unsigned.
-//   64-bit hash  h64 = (mm3(s, 0x9747B28C) << 32) | mm3(s, 0x5BD1E995)
+//   64-bit hash  h64 = (mm3(s, hm::SKETCH_SEED_HI) << 32) | mm3(s, hm::SKETCH_SEED_LO)  (murmur3.h)
 //   HyperLogLog  p in 4..16, m = 2^p; idx = h64 >> (64 - p); w = (h64 << p) mod 2^64;
 //                rho = min(clz64(w), 64 - p) + 1 with clz64(0) = 64;
 //                reg[g, idx] = max(reg[g, idx], rho)
@@ -20,73 +20,46 @@
 #include <cstring>
 #include <vector>
 
+#include "../kernels/murmur3.h"
+
 #define HM_API extern "C" __attribute__((visibility("default")))
 
 namespace {
 
-constexpr uint32_t C1 = 0xcc9e2d51u, C2 = 0x1b873593u;
-constexpr uint32_t SEED_HI = 0x9747B28Cu, SEED_LO = 0x5BD1E995u;
 constexpr int SK_HIST = 66;
 constexpr int64_t SK_PRIVATE_BYTES = int64_t(64) << 20;   // all private copies together
 constexpr int64_t SK_PARALLEL_MIN = 4096;                 // values below which one thread runs
 
-inline uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
-
-inline uint32_t premix(uint32_t k1) {
-    k1 *= C1;
-    k1 = rotl32(k1, 15);
-    return k1 * C2;
-}
-
-inline uint32_t chain(uint32_t h1, uint32_t k) {
-    h1 ^= k;
-    h1 = rotl32(h1, 13);
-    return h1 * 5 + 0xe6546b64u;
-}
-
-inline uint32_t fmix(uint32_t h1, uint32_t len) {
-    h1 ^= len;
-    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu; h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u; h1 ^= h1 >> 16;
-    return h1;
-}
-
-inline uint32_t tail_word(const uint8_t* tp, int r) {
-    uint32_t k1 = 0;
-    switch (r) {
-        case 3: k1 ^= (uint32_t)tp[2] << 16; [[fallthrough]];
-        case 2: k1 ^= (uint32_t)tp[1] << 8; [[fallthrough]];
-        case 1: k1 ^= tp[0];
-    }
-    return k1;
-}
-
+// The twin's own loops over the shared steps: 64-bit counters and the tail premix unconditional
+// (hm::murmur3_bytes, with int counters and the premix behind its switch, made bloom_add 4-6 %
+// slower here: docs/perf_notes.md "Sketches").
 inline uint32_t mm3(const uint8_t* p, int64_t len, uint32_t seed) {
     uint32_t h = seed;
     const int64_t nw = len >> 2;
     for (int64_t i = 0; i < nw; ++i) {
         uint32_t k1;
         std::memcpy(&k1, p + 4 * i, 4);               // little-endian host
-        h = chain(h, premix(k1));
+        h = hm::mm_chain(h, hm::mm_premix(k1));
     }
-    h ^= premix(tail_word(p + 4 * nw, (int)(len & 3)));   // premix(0) == 0: no tail, no change
-    return fmix(h, (uint32_t)len);
+    h ^= hm::mm_premix(hm::mm_tail_word(p + 4 * nw, (int)(len & 3)));   // 0 when no tail
+    return hm::mm_fmix(h, (uint32_t)len);
 }
 
 // one premix per word, two chains
 inline uint64_t mm3_h64(const uint8_t* p, int64_t len) {
-    uint32_t ha = SEED_HI, hb = SEED_LO;
+    uint32_t ha = hm::SKETCH_SEED_HI, hb = hm::SKETCH_SEED_LO;
     const int64_t nw = len >> 2;
     for (int64_t i = 0; i < nw; ++i) {
         uint32_t k1;
-        std::memcpy(&k1, p + 4 * i, 4);
-        const uint32_t k = premix(k1);
-        ha = chain(ha, k);
-        hb = chain(hb, k);
+        std::memcpy(&k1, p + 4 * i, 4);               // little-endian host
+        const uint32_t k = hm::mm_premix(k1);
+        ha = hm::mm_chain(ha, k);
+        hb = hm::mm_chain(hb, k);
     }
-    const uint32_t k = premix(tail_word(p + 4 * nw, (int)(len & 3)));
+    const uint32_t k = hm::mm_premix(hm::mm_tail_word(p + 4 * nw, (int)(len & 3)));   // 0 when no tail
     ha ^= k;
     hb ^= k;
-    return ((uint64_t)fmix(ha, (uint32_t)len) << 32) | fmix(hb, (uint32_t)len);
+    return ((uint64_t)hm::mm_fmix(ha, (uint32_t)len) << 32) | hm::mm_fmix(hb, (uint32_t)len);
 }
 
 inline void hll_slot(uint64_t h, int p, uint32_t& idx, uint8_t& rho) {

@@ -21,12 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define HM_HD __host__ __device__ __forceinline__
-#else
-#define HM_HD static inline __attribute__((always_inline))   // as on the device: the per-feature rules must inline into the row loop
-#endif
+#include "hd.h"   // HM_HD: the per-feature rules must inline into the row loop on both sides
 
 namespace hm_lin {
 

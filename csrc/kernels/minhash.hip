@@ -36,20 +36,6 @@ constexpr int MH_BYTES = 8192;     // bytes staged per pass
 constexpr int MH_HASHES = 256;     // hash indices per pass over the rows
 constexpr int MH_MAX_GRID = 4096;
 
-constexpr uint32_t C1 = 0xcc9e2d51u, C2 = 0x1b873593u;
-
-__device__ __forceinline__ uint32_t premix(uint32_t k1) {
-    k1 *= C1;
-    k1 = hm::mm_rotl32(k1, 15);
-    return k1 * C2;
-}
-
-__device__ __forceinline__ uint32_t fmix(uint32_t h1, uint32_t len) {
-    h1 ^= len;
-    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu; h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u; h1 ^= h1 >> 16;
-    return h1;
-}
-
 __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ nlen, const int64_t* __restrict__ rowptr, int64_t n_rows,
@@ -129,16 +115,9 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
                         for (int i = 0; i < nw; ++i) {
                             const uint32_t k1 = (uint32_t)q[4 * i] | ((uint32_t)q[4 * i + 1] << 8) |
                                                 ((uint32_t)q[4 * i + 2] << 16) | ((uint32_t)q[4 * i + 3] << 24);
-                            s_words[w0 + i] = premix(k1);
+                            s_words[w0 + i] = hm::mm_premix(k1);
                         }
-                        uint32_t k1 = 0;
-                        const int tb = nw * 4;
-                        switch (L & 3) {
-                            case 3: k1 ^= (uint32_t)q[tb + 2] << 16; [[fallthrough]];
-                            case 2: k1 ^= (uint32_t)q[tb + 1] << 8; [[fallthrough]];
-                            case 1: k1 ^= (uint32_t)q[tb];
-                        }
-                        s_tail[t] = premix(k1);        // premix(0) == 0: no tail, no change
+                        s_tail[t] = hm::mm_premix(hm::mm_tail_word(q + nw * 4, L & 3));   // 0 when no tail
                         s_wbeg[t] = w0;
                     } else {
                         s_tail[t] = 0;
@@ -163,12 +142,8 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
                         if (w0 >= 0) {
                             h1 = seed;
                             const int nw = L >> 2;
-                            for (int i = 0; i < nw; ++i) {
-                                h1 ^= s_words[w0 + i];
-                                h1 = hm::mm_rotl32(h1, 13);
-                                h1 = h1 * 5 + 0xe6546b64u;
-                            }
-                            h1 = fmix(h1 ^ s_tail[j], (uint32_t)L);
+                            for (int i = 0; i < nw; ++i) h1 = hm::mm_chain(h1, s_words[w0 + i]);
+                            h1 = hm::mm_fmix(h1 ^ s_tail[j], (uint32_t)L);
                         } else {
                             const uint8_t* q = buf + off[p + j];
                             h1 = hm::murmur3([&](int i) { return q[i]; }, L, seed);

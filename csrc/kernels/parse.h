@@ -4,9 +4,11 @@
 #pragma once
 #include <stdint.h>
 
+#include "hd.h"
+
 namespace hm {
 
-__device__ __forceinline__ bool dev_parse_int(const uint8_t* p, int n, int64_t* out) {
+HM_HD bool dev_parse_int(const uint8_t* p, int n, int64_t* out) {
     if (n <= 0 || n > 19) return false;
     int i = 0;
     bool neg = false;
@@ -26,7 +28,7 @@ __device__ __forceinline__ bool dev_parse_int(const uint8_t* p, int n, int64_t* 
 // operation) or refused, so the result always equals the host's (float)strtod.  Written as
 // three straight scans (find the exponent marker, mantissa, exponent): the single-loop form
 // with a mid-loop break refused every exponent on gfx950 (benchmarks/parse_probe.py).
-__device__ __forceinline__ bool dev_parse_float(const uint8_t* p, int n, float* out) {
+HM_HD bool dev_parse_float(const uint8_t* p, int n, float* out) {
     if (n <= 0 || n > 63) return false;
     int ep = n;                                   // exponent marker position (n = none)
     for (int i = 0; i < n; ++i) {
@@ -78,7 +80,7 @@ __device__ __forceinline__ bool dev_parse_float(const uint8_t* p, int n, float* 
     return true;
 }
 
-__device__ __forceinline__ int find_colon(const uint8_t* s, int len, int from) {
+HM_HD int find_colon(const uint8_t* s, int len, int from) {
     for (int i = from; i < len; ++i)
         if (s[i] == ':') return i;
     return -1;

@@ -4,7 +4,7 @@
 //
 // Contract (docs/compat.md "Sketches"; the classes misc.HyperLogLog / misc.Bloom are the
 // definition).  mm3 = MurmurHash3_x86_32 over the UTF-8 bytes of a value, unsigned.
-//   64-bit hash  h64 = (mm3(s, 0x9747B28C) << 32) | mm3(s, 0x5BD1E995)
+//   64-bit hash  h64 = (mm3(s, hm::SKETCH_SEED_HI) << 32) | mm3(s, hm::SKETCH_SEED_LO)  (murmur3.h)
 //   HyperLogLog  p in 4..16, m = 2^p; idx = h64 >> (64 - p); w = (h64 << p) mod 2^64;
 //                rho = min(clz64(w), 64 - p) + 1 with clz64(0) = 64 (so rho <= 65 - p);
 //                reg[g, idx] = max(reg[g, idx], rho)
@@ -53,27 +53,6 @@ constexpr int SK_MAX_GRID = 2048;
 constexpr int SK_LDS_MAX_GRID = 512;         // LDS path: docs/perf_notes.md "Sketches", grid sweep
 constexpr int SK_HIST = 66;                  // rho is in 0..65 - p <= 61; 66 as the contract says
 
-constexpr uint32_t C1 = 0xcc9e2d51u, C2 = 0x1b873593u;
-constexpr uint32_t SEED_HI = 0x9747B28Cu, SEED_LO = 0x5BD1E995u;
-
-__device__ __forceinline__ uint32_t premix(uint32_t k1) {
-    k1 *= C1;
-    k1 = hm::mm_rotl32(k1, 15);
-    return k1 * C2;
-}
-
-__device__ __forceinline__ uint32_t chain(uint32_t h1, uint32_t k) {
-    h1 ^= k;
-    h1 = hm::mm_rotl32(h1, 13);
-    return h1 * 5 + 0xe6546b64u;
-}
-
-__device__ __forceinline__ uint32_t fmix(uint32_t h1, uint32_t len) {
-    h1 ^= len;
-    h1 ^= h1 >> 16; h1 *= 0x85ebca6bu; h1 ^= h1 >> 13; h1 *= 0xc2b2ae35u; h1 ^= h1 >> 16;
-    return h1;
-}
-
 // Word i of a value (little endian); the bytes past its end are unspecified (the caller masks).
 struct LdsWords {
     const uint32_t* w;     // the aligned LDS dword that holds the first byte
@@ -99,27 +78,27 @@ template <typename Words>
 __device__ __forceinline__ uint32_t mm3(const Words& word, int len, uint32_t seed) {
     uint32_t h = seed;
     const int nw = len >> 2, r = len & 3;
-    for (int i = 0; i < nw; ++i) h = chain(h, premix(word(i)));
-    if (r) h ^= premix(word(nw) & ((1u << (8 * r)) - 1u));
-    return fmix(h, (uint32_t)len);
+    for (int i = 0; i < nw; ++i) h = hm::mm_chain(h, hm::mm_premix(word(i)));
+    if (r) h ^= hm::mm_premix(word(nw) & ((1u << (8 * r)) - 1u));
+    return hm::mm_fmix(h, (uint32_t)len);
 }
 
 // the two halves of h64: one premix per word, two chains
 template <typename Words>
 __device__ __forceinline__ uint64_t mm3_h64(const Words& word, int len) {
-    uint32_t ha = SEED_HI, hb = SEED_LO;
+    uint32_t ha = hm::SKETCH_SEED_HI, hb = hm::SKETCH_SEED_LO;
     const int nw = len >> 2, r = len & 3;
     for (int i = 0; i < nw; ++i) {
-        const uint32_t k = premix(word(i));
-        ha = chain(ha, k);
-        hb = chain(hb, k);
+        const uint32_t k = hm::mm_premix(word(i));
+        ha = hm::mm_chain(ha, k);
+        hb = hm::mm_chain(hb, k);
     }
     if (r) {
-        const uint32_t k = premix(word(nw) & ((1u << (8 * r)) - 1u));
+        const uint32_t k = hm::mm_premix(word(nw) & ((1u << (8 * r)) - 1u));
         ha ^= k;
         hb ^= k;
     }
-    return ((uint64_t)fmix(ha, (uint32_t)len) << 32) | fmix(hb, (uint32_t)len);
+    return ((uint64_t)hm::mm_fmix(ha, (uint32_t)len) << 32) | hm::mm_fmix(hb, (uint32_t)len);
 }
 
 // The front end: calls op(s, words, len) once for every value s in 0..n-1, on the lane that owns

@@ -125,6 +125,19 @@ def stream_of(device=None) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def call_hip(name: str, device, *args) -> None:
+    """Launch kernel entry ``name`` on the current stream of ``device`` (the stream is the last
+    argument of every launcher); a launch error raises."""
+    check(getattr(hip(), name)(*args, stream_of(device)), name)
+
+
+def call_host(name: str, *args) -> None:
+    """Run ``name``'s CPU twin ``<name>_cpu`` of the host library; a non-zero return raises."""
+    rc = getattr(host(), name + "_cpu")(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name}_cpu failed: {rc}")
+
+
 def i32arr(vals):
     a = np.asarray(vals, dtype=np.int32)
     return a, a.ctypes.data

@@ -16,11 +16,11 @@ the OpenMP twin is sequential in time, in the Python path's operation order.  Ev
 from __future__ import annotations
 
 import ctypes as C
-import operator
 
 import torch
 
 from .. import _native
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -32,18 +32,6 @@ CHUNK = 256         # points per workgroup, one lane each
 K_MAX = 32          # the covariance sums and Levinson coefficients of a point stay in registers
 T_MAX = 1024
 LOSSES = ("hellinger", "logloss")
-
-
-def _int_in(v, name: str, lo: int, hi: int) -> int:
-    try:
-        if isinstance(v, bool):
-            raise TypeError
-        v = operator.index(v)
-    except TypeError:
-        raise ValueError(f"changefinder: {name} must be an int {lo}..{hi}, got {v!r}") from None
-    if v < lo or v > hi:
-        raise ValueError(f"changefinder: {name} must be {lo}..{hi}, got {v}")
-    return v
 
 
 def _rate(v, name: str) -> float:
@@ -66,11 +54,11 @@ def supports(k, r1, r2, T1, T2, loss1, loss2) -> bool:
     before it chooses this engine): ``1 <= k <= 32``, ``0 < r1, r2 < 1``, ``1 <= T1, T2 <= 1024``,
     losses hellinger or logloss."""
     try:
-        _int_in(k, "k", 1, K_MAX)
+        _args.int_in("changefinder", k, "k", 1, K_MAX)
         _rate(r1, "r1")
         _rate(r2, "r2")
-        _int_in(T1, "T1", 1, T_MAX)
-        _int_in(T2, "T2", 1, T_MAX)
+        _args.int_in("changefinder", T1, "T1", 1, T_MAX)
+        _args.int_in("changefinder", T2, "T2", 1, T_MAX)
         _loss(loss1, "loss1")
         _loss(loss2, "loss2")
     except ValueError:
@@ -90,18 +78,19 @@ def changefinder_scores(x: torch.Tensor, k: int = 7, r1: float = 0.02, r2: float
         raise ValueError(f"changefinder: x must be {torch.float64}, got {x.dtype}")
     if x.dim() not in (1, 2, 3):
         raise ValueError(f"changefinder: x must be [N], [S, N] or [S, N, D], got shape {tuple(x.shape)}")
-    k = _int_in(k, "k", 1, K_MAX)
+    k = _args.int_in("changefinder", k, "k", 1, K_MAX)
     r1, r2 = _rate(r1, "r1"), _rate(r2, "r2")
-    T1, T2 = _int_in(T1, "T1", 1, T_MAX), _int_in(T2, "T2", 1, T_MAX)
+    T1 = _args.int_in("changefinder", T1, "T1", 1, T_MAX)
+    T2 = _args.int_in("changefinder", T2, "T2", 1, T_MAX)
     l1, l2 = _loss(loss1, "loss1"), _loss(loss2, "loss2")
     x3 = x.reshape(1, -1, 1) if x.dim() == 1 else x[:, :, None] if x.dim() == 2 else x
     S, N, D = x3.shape
-    bad = ~torch.isfinite(x3)
-    if bool(bad.any()):
-        at = int(torch.nonzero(bad.reshape(-1))[0])
-        where = (at // (N * D), at // D % N, at % D)
-        where = where[1] if x.dim() == 1 else where[:x.dim()]
-        raise ValueError(f"changefinder: x[{where}] is not finite ({float(x3.reshape(-1)[at])})")
+
+    def where(at):
+        index = (at // (N * D), at // D % N, at % D)
+        return index[1] if x.dim() == 1 else index[:x.dim()]
+
+    _args.all_finite("changefinder", x3, where)
     out_shape = tuple(x.shape[:2]) if x.dim() == 3 else tuple(x.shape)
     new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=x.device)   # noqa: E731
     outlier, changepoint = new(S, N), new(S, N)
@@ -123,14 +112,11 @@ def changefinder_scores(x: torch.Tensor, k: int = 7, r1: float = 0.02, r2: float
         agg1, car1 = new(S * D * nch), new(S * D * nch)
         aggc, carc = new(S * D * nch * (k + 1)), new(S * D * nch * (k + 1))
         e2 = new(S * D, N)
-        rc = _native.hip().hm_changefinder(
-            p(rows), S, D, N, k, r1, r2, T1, T2, l1, l2, p(pw1), p(pw2), p(agg1), p(car1), p(aggc),
-            p(carc), p(e2), p(score), p(y), p(outlier), p(changepoint), _native.stream_of(x.device))
-        _native.check(rc, "hm_changefinder")
+        _native.call_hip(
+            "hm_changefinder", x.device, p(rows), S, D, N, k, r1, r2, T1, T2, l1, l2, p(pw1), p(pw2),
+            p(agg1), p(car1), p(aggc), p(carc), p(e2), p(score), p(y), p(outlier), p(changepoint))
     else:
-        rc = _native.host().hm_changefinder_cpu(
-            p(rows), S, D, N, k, r1, r2, T1, T2, l1, l2, *([0] * 7), p(score), p(y), p(outlier),
-            p(changepoint))
-        if rc != 0:
-            raise RuntimeError(f"hm_changefinder_cpu failed: {rc}")
+        _native.call_host(
+            "hm_changefinder", p(rows), S, D, N, k, r1, r2, T1, T2, l1, l2, *([0] * 7), p(score), p(y),
+            p(outlier), p(changepoint))
     return outlier.reshape(out_shape), changepoint.reshape(out_shape)

@@ -413,6 +413,4 @@ def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torc
             b = state["bias"]
             b[0] = -b[1] / ((hyper.beta + b[2].sqrt()) / hyper.alpha)
     else:
-        rc = _native.host().hm_ffm_step_cpu(*args)
-        if rc != 0:
-            raise RuntimeError(f"hm_ffm_step_cpu failed: {rc}")
+        _native.call_host("hm_ffm_step", *args)

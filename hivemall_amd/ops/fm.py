@@ -180,9 +180,7 @@ def fm_step(state: dict, indptr: torch.Tensor, idx: torch.Tensor, val: torch.Ten
     else:
         assert not bf16, "CPU FM engine keeps V in fp32"
         assert V.is_contiguous() and w.is_contiguous(), "CPU FM engine: contiguous w and V"
-        rc = _native.host().hm_fm_step_cpu(*args)
-        if rc != 0:
-            raise RuntimeError(f"hm_fm_step_cpu failed: {rc}")
+        _native.call_host("hm_fm_step", *args)
 
 
 _P = _native.c_p

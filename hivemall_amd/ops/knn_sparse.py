@@ -17,11 +17,11 @@ tensors run the gfx950 kernels on the current stream, CPU tensors the OpenMP twi
 from __future__ import annotations
 
 import ctypes as C
-import operator
 
 import torch
 
 from .. import _native
+from . import _args
 from .slim import KMAX, check_csc
 
 _P = C.c_void_p
@@ -34,33 +34,6 @@ _native.register_host("hm_knn_cols_cpu", [_P, _P, _P, C.c_int, _P, _P, _P, _P, _
                                           C.c_int, _P, _P])
 
 TILE_MAX = 16384    # candidate columns per pass: 128 KiB of fp64 accumulators in one CU's LDS
-
-
-def _want(t, name: str, dtype, ndim: int) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"knn: {name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"knn: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"knn: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
-
-
-def _same_device(ts, names) -> None:
-    for t, nm in zip(ts[1:], names[1:]):
-        if t.device != ts[0].device:
-            raise ValueError(f"knn: {nm} is on {t.device}, {names[0]} on {ts[0].device}")
-
-
-def _int_in(v, name: str, lo: int, hi: int) -> int:
-    try:
-        if isinstance(v, bool):
-            raise TypeError
-        v = operator.index(v)
-    except TypeError:
-        raise ValueError(f"knn: {name} must be an int in {lo}..{hi}, got {v!r}") from None
-    if not lo <= v <= hi:
-        raise ValueError(f"knn: {name} must be in {lo}..{hi}, got {v}")
-    return v
 
 
 def _check_rows(rows: torch.Tensor, n_rows) -> int:
@@ -94,22 +67,19 @@ def csc_transpose(colptr: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor, 
 def col_rnorm(colptr: torch.Tensor, vals: torch.Tensor) -> torch.Tensor:
     """fp64 [C]: ``1 / sqrt(sum v^2)`` of every column, 0 for an empty one.  The summation order
     is fixed, so identical columns get bit-identical norms."""
-    _want(colptr, "colptr", torch.int64, 1)
-    _want(vals, "vals", torch.float64, 1)
-    _same_device((colptr, vals), ("colptr", "vals"))
+    _args.want("knn", colptr, "colptr", torch.int64, 1)
+    _args.want("knn", vals, "vals", torch.float64, 1)
+    _args.same_device("knn", (colptr, vals), ("colptr", "vals"))
     n_cols = colptr.numel() - 1
     out = torch.empty(max(n_cols, 0), dtype=torch.float64, device=vals.device)
     if n_cols <= 0:
         return out
     colptr, vals = colptr.contiguous(), vals.contiguous()
-    p = _native.ptr
+    args = (_native.ptr(colptr), _native.ptr(vals), n_cols, _native.ptr(out))
     if vals.is_cuda:
-        rc = _native.hip().hm_knn_rnorm(p(colptr), p(vals), n_cols, p(out), _native.stream_of(vals.device))
-        _native.check(rc, "hm_knn_rnorm")
+        _native.call_hip("hm_knn_rnorm", vals.device, *args)
     else:
-        rc = _native.host().hm_knn_rnorm_cpu(p(colptr), p(vals), n_cols, p(out))
-        if rc != 0:
-            raise RuntimeError(f"hm_knn_rnorm_cpu failed: {rc}")
+        _native.call_host("hm_knn_rnorm", *args)
     return out
 
 
@@ -139,13 +109,13 @@ def knn_cols(colptr: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor, k: in
     else:
         n_cols = colptr.numel() - 1
         n_rows = (int(rows.max()) + 1 if rows.numel() else 0) if n_rows is None else int(n_rows)
-    k = _int_in(k, "k", 1, KMAX)
-    tile = TILE_MAX if tile is None else _int_in(tile, "tile", 1, TILE_MAX)
+    k = _args.int_in("knn", k, "k", 1, KMAX)
+    tile = TILE_MAX if tile is None else _args.int_in("knn", tile, "tile", 1, TILE_MAX)
     dev = colptr.device
     if query is None:
         query = torch.arange(n_cols, dtype=torch.int32, device=dev)
-    _want(query, "query", torch.int32, 1)
-    _same_device((colptr, query), ("colptr", "query"))
+    _args.want("knn", query, "query", torch.int32, 1)
+    _args.same_device("knn", (colptr, query), ("colptr", "query"))
     n = query.numel()
     if n and (int(query.min()) < 0 or int(query.max()) >= n_cols):
         raise ValueError(f"knn: query column ids must be in 0..{n_cols - 1}")
@@ -170,13 +140,9 @@ def knn_cols_prepared(colptr, rows, vals, transposed, rnorm, query, k: int, tile
         # heaviest queries first, so that the long workgroups start early
         work = query_work(colptr, rows, rowptr, query)
         order = torch.sort(work, descending=True, stable=True).indices.to(torch.int32)
-        rc = _native.hip().hm_knn_cols(p(colptr), p(rows), p(vals), n_cols, p(rowptr), p(cols), p(rvals),
-                                       p(rnorm), p(query), p(order), n, k, tile, p(idx), p(score),
-                                       _native.stream_of(dev))
-        _native.check(rc, "hm_knn_cols")
+        _native.call_hip("hm_knn_cols", dev, p(colptr), p(rows), p(vals), n_cols, p(rowptr), p(cols), p(rvals),
+                         p(rnorm), p(query), p(order), n, k, tile, p(idx), p(score))
     else:
-        rc = _native.host().hm_knn_cols_cpu(p(colptr), p(rows), p(vals), n_cols, p(rowptr), p(cols),
-                                            p(rvals), p(rnorm), p(query), n, k, tile, p(idx), p(score))
-        if rc != 0:
-            raise RuntimeError(f"hm_knn_cols_cpu failed: {rc}")
+        _native.call_host("hm_knn_cols", p(colptr), p(rows), p(vals), n_cols, p(rowptr), p(cols), p(rvals),
+                          p(rnorm), p(query), n, k, tile, p(idx), p(score))
     return idx, score

@@ -133,9 +133,7 @@ def train_pass(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.T
         rc = _native.hip().hm_linear_train(*args, p(st.gacc), p(st.tlist), _native.stream_of(dev))
         _native.check(rc, "hm_linear_train")
     else:
-        rc = _native.host().hm_linear_train_cpu(*args)
-        if rc != 0:
-            raise RuntimeError(f"hm_linear_train_cpu failed: {rc}")
+        _native.call_host("hm_linear_train", *args)
     return loss
 
 

@@ -16,12 +16,12 @@ current stream, CPU tensors the OpenMP twin; both are integer only and agree bit
 from __future__ import annotations
 
 import ctypes as C
-import operator
 
 import numpy as np
 import torch
 
 from .. import _native
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -38,27 +38,6 @@ HASHES_PER_PASS = 256   # MH_HASHES
 MAX_GRID = 4096         # MH_MAX_GRID
 
 
-def _want(t, name: str, dtype, ndim: int) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"minhash: {name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"minhash: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"minhash: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
-
-
-def _int_in(v, name: str, lo: int, hi: int) -> int:
-    try:
-        if isinstance(v, bool):
-            raise TypeError
-        v = operator.index(v)
-    except TypeError:
-        raise ValueError(f"minhash: {name} must be an int in {lo}..{hi}, got {v!r}") from None
-    if not lo <= v <= hi:
-        raise ValueError(f"minhash: {name} must be in {lo}..{hi}, got {v}")
-    return v
-
-
 def _check_ptr(p: torch.Tensor, name: str) -> None:
     if p.numel() < 1:
         raise ValueError(f"minhash: {name} must hold at least one offset")
@@ -68,32 +47,19 @@ def _check_ptr(p: torch.Tensor, name: str) -> None:
         raise ValueError(f"minhash: {name} must be non-decreasing")
 
 
-def _pad16(buf: torch.Tensor) -> torch.Tensor:
-    """The kernel stages bytes in whole aligned 16-B chunks: a base that is 16-B aligned and a
-    length that is a multiple of 16 keep every such chunk inside the allocation."""
-    n = buf.numel()
-    if n and n % 16 == 0 and buf.data_ptr() % 16 == 0:
-        return buf
-    out = torch.zeros(max(16, (n + 15) // 16 * 16), dtype=torch.uint8, device=buf.device)
-    out[:n] = buf
-    return out
-
-
 def minhash_signatures(buf: torch.Tensor, off: torch.Tensor, nlen: torch.Tensor, rowptr: torch.Tensor,
                        num_hashes: int, seed0: int = 0, *, check: bool = True) -> torch.Tensor:
     """int32 [n_rows, num_hashes]: the minhash signature of every row (uint32 bit patterns).
     ``check=False`` skips the passes over ``off``, ``nlen`` and ``rowptr`` (monotone offsets, name
     lengths inside their strings) for a caller that built them itself, as ``pack_feature_column``
     does; dtypes, shapes, devices and the two scalars are always checked."""
-    _want(buf, "buf", torch.uint8, 1)
-    _want(off, "off", torch.int64, 1)
-    _want(nlen, "nlen", torch.int32, 1)
-    _want(rowptr, "rowptr", torch.int64, 1)
-    for t, nm in ((off, "off"), (nlen, "nlen"), (rowptr, "rowptr")):
-        if t.device != buf.device:
-            raise ValueError(f"minhash: {nm} is on {t.device}, buf on {buf.device}")
-    H = _int_in(num_hashes, "num_hashes", 1, H_MAX)
-    seed0 = _int_in(seed0, "seed0", 0, 2**32 - 1)
+    _args.want("minhash", buf, "buf", torch.uint8, 1)
+    _args.want("minhash", off, "off", torch.int64, 1)
+    _args.want("minhash", nlen, "nlen", torch.int32, 1)
+    _args.want("minhash", rowptr, "rowptr", torch.int64, 1)
+    _args.same_device("minhash", (buf, off, nlen, rowptr), ("buf", "off", "nlen", "rowptr"))
+    H = _args.int_in("minhash", num_hashes, "num_hashes", 1, H_MAX)
+    seed0 = _args.int_in("minhash", seed0, "seed0", 0, 2**32 - 1)
     if check:
         _check_ptr(off, "off")
         _check_ptr(rowptr, "rowptr")
@@ -116,26 +82,23 @@ def minhash_signatures(buf: torch.Tensor, off: torch.Tensor, nlen: torch.Tensor,
         return out
     buf, off, nlen, rowptr = (t.contiguous() for t in (buf, off, nlen, rowptr))
     p = _native.ptr
+    rest = (p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out))
     if buf.is_cuda:
-        buf = _pad16(buf)
-        rc = _native.hip().hm_minhash_sig(p(buf), p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out),
-                                          _native.stream_of(dev))
-        _native.check(rc, "hm_minhash_sig")
+        buf = _args.pad16(buf)
+        _native.call_hip("hm_minhash_sig", dev, p(buf), *rest)
     else:
         if buf.numel() == 0:
             buf = torch.zeros(1, dtype=torch.uint8)
-        rc = _native.host().hm_minhash_sig_cpu(p(buf), p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out))
-        if rc != 0:
-            raise RuntimeError(f"hm_minhash_sig_cpu failed: {rc}")
+        _native.call_host("hm_minhash_sig", p(buf), *rest)
     return out
 
 
 def cluster_ids(sig: torch.Tensor, key_groups: int) -> torch.Tensor:
     """int32 [n_rows, H / key_groups]: every run of ``key_groups`` hashes folded as ``minhashes``
     does it, ``h = (h * 31 + v) & 0x7FFFFFFF`` over the unsigned ``v``, starting from 0."""
-    _want(sig, "sig", torch.int32, 2)
+    _args.want("minhash", sig, "sig", torch.int32, 2)
     H = sig.shape[1]
-    kg = _int_in(key_groups, "key_groups", 1, max(H, 1))
+    kg = _args.int_in("minhash", key_groups, "key_groups", 1, max(H, 1))
     if H % kg:
         raise ValueError(f"minhash: key_groups = {kg} does not divide the {H} hashes of sig")
     v = (sig.long() & 0xFFFFFFFF).reshape(sig.shape[0], H // kg, kg)
@@ -147,8 +110,8 @@ def cluster_ids(sig: torch.Tensor, key_groups: int) -> torch.Tensor:
 
 def bbit_pack(sig: torch.Tensor, b: int) -> list:
     """The hex strings of ``bbit_minhash``: the lowest ``b`` bits of hash ``i`` at bit ``i * b``."""
-    _want(sig, "sig", torch.int32, 2)
-    b = _int_in(b, "b", 1, 32)
+    _args.want("minhash", sig, "sig", torch.int32, 2)
+    b = _args.int_in("minhash", b, "b", 1, 32)
     n, H = sig.shape
     if n == 0 or H == 0:
         return ["0"] * n

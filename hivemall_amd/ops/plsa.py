@@ -34,6 +34,7 @@ import ctypes as C
 import torch
 
 from .. import _native
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -49,23 +50,8 @@ KMAX = 256                  # topics: lanes of one workgroup span them (4 per la
 EM_STAGE_FLOATS = 12 * 1024   # floats of pwzT rows (nd * K) one document stages in LDS (plsa.hip)
 
 
-def _want(t, name: str, dtype, ndim: int) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"plsa: {name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"plsa: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"plsa: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
-
-
-def _same_device(ts, names) -> None:
-    for t, nm in zip(ts[1:], names[1:]):
-        if t.device != ts[0].device:
-            raise ValueError(f"plsa: {nm} is on {t.device}, {names[0]} on {ts[0].device}")
-
-
 def _want_pwzT(pwzT) -> tuple:
-    _want(pwzT, "pwzT", torch.float32, 2)
+    _args.want("plsa", pwzT, "pwzT", torch.float32, 2)
     V, K = pwzT.shape
     if K < 1 or K > KMAX:
         raise ValueError(f"plsa: {K} topics, the native engine holds 1..{KMAX}")
@@ -80,10 +66,10 @@ def _rises(off: torch.Tensor, n: int) -> bool:
 def check_doc_batch(doc_off: torch.Tensor, wid: torch.Tensor, cnt: torch.Tensor, V: int) -> int:
     """Validate a mini-batch's CSR triple (dtypes, shapes, devices, ``doc_off`` rising from 0 to
     ``N``, ``0 <= wid < V``); returns the number of documents."""
-    _want(doc_off, "doc_off", torch.int32, 1)
-    _want(wid, "wid", torch.int32, 1)
-    _want(cnt, "cnt", torch.float32, 1)
-    _same_device((doc_off, wid, cnt), ("doc_off", "wid", "cnt"))
+    _args.want("plsa", doc_off, "doc_off", torch.int32, 1)
+    _args.want("plsa", wid, "wid", torch.int32, 1)
+    _args.want("plsa", cnt, "cnt", torch.float32, 1)
+    _args.same_device("plsa", (doc_off, wid, cnt), ("doc_off", "wid", "cnt"))
     N = wid.numel()
     if cnt.numel() != N:
         raise ValueError(f"plsa: wid has {N} entries, cnt {cnt.numel()}")
@@ -100,10 +86,10 @@ def check_word_index(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Ten
     rising from 0 to ``N`` over ``U + 1`` entries, ``perm`` a permutation of ``0..N-1`` that
     ascends inside every word's run and, when the batch's ``wid`` is given, sorts it into
     ``uniq``'s runs.  Returns ``U``."""
-    _want(word_off, "word_off", torch.int32, 1)
-    _want(perm, "perm", torch.int32, 1)
-    _want(uniq, "uniq", torch.int32, 1)
-    _same_device((word_off, perm, uniq), ("word_off", "perm", "uniq"))
+    _args.want("plsa", word_off, "word_off", torch.int32, 1)
+    _args.want("plsa", perm, "perm", torch.int32, 1)
+    _args.want("plsa", uniq, "uniq", torch.int32, 1)
+    _args.same_device("plsa", (word_off, perm, uniq), ("word_off", "perm", "uniq"))
     N, U = perm.numel(), uniq.numel()
     if word_off.numel() != U + 1 or not _rises(word_off, N):
         raise ValueError("plsa: word_off must have len(uniq) + 1 entries rising from 0 to len(perm)")
@@ -119,8 +105,8 @@ def check_word_index(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Ten
         if N > 1 and bool(((perm[1:] <= perm[:-1]) & (run[1:] == run[:-1])).any()):
             raise ValueError("plsa: perm must ascend inside every word's run (sorted by (word, index))")
         if wid is not None:
-            _want(wid, "wid", torch.int32, 1)
-            _same_device((perm, wid), ("perm", "wid"))
+            _args.want("plsa", wid, "wid", torch.int32, 1)
+            _args.same_device("plsa", (perm, wid), ("perm", "wid"))
             if wid.numel() != N or not torch.equal(wid[perm.long()], uniq[run]):
                 raise ValueError("plsa: perm / word_off / uniq are not the sorted index of wid")
     return U
@@ -129,7 +115,7 @@ def check_word_index(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Ten
 def batch_index(wid: torch.Tensor):
     """``(perm, word_off, uniq)`` of a batch's word ids int32 [N]: a stable sort (non-zero
     indices by (word, index)) and its runs, on ``wid``'s device."""
-    _want(wid, "wid", torch.int32, 1)
+    _args.want("plsa", wid, "wid", torch.int32, 1)
     srt, perm = torch.sort(wid, stable=True)
     uniq, counts = torch.unique_consecutive(srt, return_counts=True)
     word_off = torch.zeros(uniq.numel() + 1, dtype=torch.int32, device=wid.device)
@@ -150,13 +136,13 @@ def plsa_doc_em(doc_off: torch.Tensor, wid: torch.Tensor, cnt: torch.Tensor, pwz
     if check:
         B = check_doc_batch(doc_off, wid, cnt, V)
     else:
-        _want(doc_off, "doc_off", torch.int32, 1)
-        _want(wid, "wid", torch.int32, 1)
-        _want(cnt, "cnt", torch.float32, 1)
+        _args.want("plsa", doc_off, "doc_off", torch.int32, 1)
+        _args.want("plsa", wid, "wid", torch.int32, 1)
+        _args.want("plsa", cnt, "cnt", torch.float32, 1)
         if doc_off.numel() < 1 or cnt.numel() != wid.numel():
             raise ValueError("plsa: doc_off must have B + 1 entries and wid / cnt the same length")
         B = doc_off.numel() - 1
-    _same_device((pwzT, doc_off, wid, cnt), ("pwzT", "doc_off", "wid", "cnt"))
+    _args.same_device("plsa", (pwzT, doc_off, wid, cnt), ("pwzT", "doc_off", "wid", "cnt"))
     dev, N = pwzT.device, wid.numel()
     pzd = torch.empty((B, K), dtype=torch.float32, device=dev)
     contrib = torch.empty((N, K), dtype=torch.float32, device=dev)
@@ -165,15 +151,11 @@ def plsa_doc_em(doc_off: torch.Tensor, wid: torch.Tensor, cnt: torch.Tensor, pwz
         return pzd, contrib, iters
     doc_off, wid, cnt, pwzT = (t.contiguous() for t in (doc_off, wid, cnt, pwzT))
     p = _native.ptr
+    args = (p(doc_off), p(wid), p(cnt), p(pwzT), B, K, float(delta), int(max_iter), p(pzd), p(contrib), p(iters))
     if pwzT.is_cuda:
-        rc = _native.hip().hm_plsa_doc_em(p(doc_off), p(wid), p(cnt), p(pwzT), B, K, float(delta),
-                                          int(max_iter), p(pzd), p(contrib), p(iters), _native.stream_of(dev))
-        _native.check(rc, "hm_plsa_doc_em")
+        _native.call_hip("hm_plsa_doc_em", dev, *args)
     else:
-        rc = _native.host().hm_plsa_doc_em_cpu(p(doc_off), p(wid), p(cnt), p(pwzT), B, K, float(delta),
-                                               int(max_iter), p(pzd), p(contrib), p(iters))
-        if rc != 0:
-            raise RuntimeError(f"hm_plsa_doc_em_cpu failed: {rc}")
+        _native.call_host("hm_plsa_doc_em", *args)
     return pzd, contrib, iters
 
 
@@ -200,17 +182,17 @@ def plsa_mstep(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Tensor, c
     V, K = _want_pwzT(pwzT)
     if not pwzT.is_contiguous():
         raise ValueError("plsa_mstep: pwzT is updated in place and must be contiguous")
-    _want(contrib, "contrib", torch.float32, 2)
+    _args.want("plsa", contrib, "contrib", torch.float32, 2)
     if check:
         U = check_word_index(word_off, perm, uniq, V, wid)
     else:
-        _want(word_off, "word_off", torch.int32, 1)
-        _want(perm, "perm", torch.int32, 1)
-        _want(uniq, "uniq", torch.int32, 1)
+        _args.want("plsa", word_off, "word_off", torch.int32, 1)
+        _args.want("plsa", perm, "perm", torch.int32, 1)
+        _args.want("plsa", uniq, "uniq", torch.int32, 1)
         U = uniq.numel()
         if word_off.numel() != U + 1:
             raise ValueError("plsa: word_off must have len(uniq) + 1 entries")
-    _same_device((pwzT, word_off, perm, uniq, contrib), ("pwzT", "word_off", "perm", "uniq", "contrib"))
+    _args.same_device("plsa", (pwzT, word_off, perm, uniq, contrib), ("pwzT", "word_off", "perm", "uniq", "contrib"))
     if tuple(contrib.shape) != (perm.numel(), K):
         raise ValueError(f"plsa: contrib must be [{perm.numel()}, {K}], got {tuple(contrib.shape)}")
     if U > V:
@@ -220,21 +202,17 @@ def plsa_mstep(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Tensor, c
     if scratch is None:
         scratch = mstep_scratch(U, V, K, dev)
     else:
-        _want(scratch, "scratch", torch.int32, 1)
-        _same_device((pwzT, scratch), ("pwzT", "scratch"))
+        _args.want("plsa", scratch, "scratch", torch.int32, 1)
+        _args.same_device("plsa", (pwzT, scratch), ("pwzT", "scratch"))
         if scratch.numel() < need or not scratch.is_contiguous():
             raise ValueError(f"plsa: scratch must be contiguous with {need} entries, got {scratch.numel()}")
     if V == 0:
         return pwzT
     word_off, perm, uniq, contrib = (t.contiguous() for t in (word_off, perm, uniq, contrib))
     p = _native.ptr
+    args = (p(word_off), p(perm), p(uniq), p(contrib), U, V, K, float(alpha), p(pwzT), p(scratch))
     if pwzT.is_cuda:
-        rc = _native.hip().hm_plsa_mstep(p(word_off), p(perm), p(uniq), p(contrib), U, V, K, float(alpha),
-                                         p(pwzT), p(scratch), _native.stream_of(dev))
-        _native.check(rc, "hm_plsa_mstep")
+        _native.call_hip("hm_plsa_mstep", dev, *args)
     else:
-        rc = _native.host().hm_plsa_mstep_cpu(p(word_off), p(perm), p(uniq), p(contrib), U, V, K,
-                                              float(alpha), p(pwzT), p(scratch))
-        if rc != 0:
-            raise RuntimeError(f"hm_plsa_mstep_cpu failed: {rc}")
+        _native.call_host("hm_plsa_mstep", *args)
     return pwzT

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from .minhash import _int_in as _mh_int_in, _pad16
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -61,30 +61,12 @@ LDS_MAX_GRID = 512          # SK_LDS_MAX_GRID
 CALLS = {"hll_registers": 0, "hll_histogram": 0, "bloom_bits": 0, "bloom_test": 0}
 
 
-def _want(t, name: str, dtype, ndim: int) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"sketch: {name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"sketch: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"sketch: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
-
-
-def _int_in(v, name: str, lo: int, hi: int) -> int:
-    try:
-        return _mh_int_in(v, name, lo, hi)
-    except ValueError as e:
-        raise ValueError(str(e).replace("minhash:", "sketch:", 1)) from None
-
-
 def _column(buf, off, ids, ids_name: str, n_ids: int, check: bool):
     """The checks shared by every entry; returns n."""
-    _want(buf, "buf", torch.uint8, 1)
-    _want(off, "off", torch.int64, 1)
-    _want(ids, ids_name, torch.int32, 1)
-    for t, nm in ((off, "off"), (ids, ids_name)):
-        if t.device != buf.device:
-            raise ValueError(f"sketch: {nm} is on {t.device}, buf on {buf.device}")
+    _args.want("sketch", buf, "buf", torch.uint8, 1)
+    _args.want("sketch", off, "off", torch.int64, 1)
+    _args.want("sketch", ids, ids_name, torch.int32, 1)
+    _args.same_device("sketch", (buf, off, ids), ("buf", "off", ids_name))
     if off.numel() < 1:
         raise ValueError("sketch: off must hold at least one offset")
     n = off.numel() - 1
@@ -108,7 +90,7 @@ def _column(buf, off, ids, ids_name: str, n_ids: int, check: bool):
 
 def _state(t, name: str, shape: tuple, device) -> torch.Tensor:
     """An in/out register file or bitmap: the caller's own tensor, updated in place."""
-    _want(t, name, torch.uint8, 2)
+    _args.want("sketch", t, name, torch.uint8, 2)
     if tuple(t.shape) != shape:
         raise ValueError(f"sketch: {name} must have shape {shape}, got {tuple(t.shape)}")
     if t.device != device:
@@ -122,19 +104,14 @@ def _host_buf(buf: torch.Tensor) -> torch.Tensor:
     return buf if buf.numel() else torch.zeros(1, dtype=torch.uint8)
 
 
-def _host_rc(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed: {rc}")
-
-
 def hll_registers(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: int, p: int,
                   reg: torch.Tensor | None = None, *, check: bool = True,
                   _lds_grid: int = 0) -> torch.Tensor:
     """uint8 ``[G, 2^p]``: the HyperLogLog registers of every group.  ``reg`` is in/out: the call
     merges into it (and returns it).  ``check=False`` skips the passes over ``off`` and ``gid`` for
     a caller that built them itself."""
-    G = _int_in(G, "G", 1, 2**31 - 1)
-    p = _int_in(p, "p", P_MIN, P_MAX)
+    G = _args.int_in("sketch", G, "G", 1, 2**31 - 1)
+    p = _args.int_in("sketch", p, "p", P_MIN, P_MAX)
     if (G << p) > 2**31 - 16:
         raise ValueError(f"sketch: G * 2^p = {G << p} registers, at most 2^31 - 16")
     n = _column(buf, off, gid, "gid", G, check)
@@ -149,18 +126,15 @@ def hll_registers(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: in
     off, gid = off.contiguous(), gid.contiguous()
     ptr = _native.ptr
     if buf.is_cuda:
-        buf = _pad16(buf.contiguous())
+        buf = _args.pad16(buf.contiguous())
         if _lds_grid:                                     # benchmarks/sketch_bench.py --sweep
-            rc = _native.hip().hm_hll_update_grid(ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg),
-                                                  int(_lds_grid), _native.stream_of(dev))
+            _native.call_hip("hm_hll_update_grid", dev, ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg),
+                             int(_lds_grid))
         else:
-            rc = _native.hip().hm_hll_update(ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg),
-                                             _native.stream_of(dev))
-        _native.check(rc, "hm_hll_update")
+            _native.call_hip("hm_hll_update", dev, ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg))
     else:
         buf = _host_buf(buf.contiguous())
-        _host_rc(_native.host().hm_hll_update_cpu(ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg)),
-                 "hm_hll_update_cpu")
+        _native.call_host("hm_hll_update", ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg))
     return reg
 
 
@@ -174,7 +148,7 @@ def _p_of(reg: torch.Tensor) -> int:
 
 def hll_histogram(reg: torch.Tensor) -> torch.Tensor:
     """int32 ``[G, 66]``: how many registers of each group hold each value."""
-    _want(reg, "reg", torch.uint8, 2)
+    _args.want("sketch", reg, "reg", torch.uint8, 2)
     p = _p_of(reg)
     G = reg.shape[0]
     if G > 2**31 - 1:
@@ -185,19 +159,18 @@ def hll_histogram(reg: torch.Tensor) -> torch.Tensor:
     CALLS["hll_histogram"] += 1
     if G == 0:
         return hist
-    ptr = _native.ptr
+    args = (_native.ptr(reg), G, p, _native.ptr(hist))
     if reg.is_cuda:
-        rc = _native.hip().hm_hll_hist(ptr(reg), G, p, ptr(hist), _native.stream_of(reg.device))
-        _native.check(rc, "hm_hll_hist")
+        _native.call_hip("hm_hll_hist", reg.device, *args)
     else:
-        _host_rc(_native.host().hm_hll_hist_cpu(ptr(reg), G, p, ptr(hist)), "hm_hll_hist_cpu")
+        _native.call_host("hm_hll_hist", *args)
     return hist
 
 
 def hll_estimate(hist, p: int) -> list:
     """The cardinality estimate of every group, computed on the host from its histogram with the
     formulas of ``misc.HyperLogLog.cardinality``."""
-    p = _int_in(p, "p", P_MIN, P_MAX)
+    p = _args.int_in("sketch", p, "p", P_MIN, P_MAX)
     h = hist.cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
     if h.ndim != 2 or h.shape[1] != HIST_BINS:
         raise ValueError(f"sketch: hist must have shape [G, {HIST_BINS}], got {tuple(h.shape)}")
@@ -220,17 +193,17 @@ def hll_estimate(hist, p: int) -> list:
 
 
 def _bloom_mk(m, k) -> tuple:
-    m = _int_in(m, "m", M_MIN, M_MAX)
+    m = _args.int_in("sketch", m, "m", M_MIN, M_MAX)
     if m % 32:
         raise ValueError(f"sketch: m must be a multiple of 32, got {m}")
-    return m, _int_in(k, "k", 1, K_MAX)
+    return m, _args.int_in("sketch", k, "k", 1, K_MAX)
 
 
 def bloom_bits(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: int, m: int = 65536, k: int = 4,
                bits: torch.Tensor | None = None, *, check: bool = True) -> torch.Tensor:
     """uint8 ``[G, m / 8]``: the Bloom filter of every group (the bytes of ``misc.Bloom.bits``).
     ``bits`` is in/out: the call merges into it (and returns it)."""
-    G = _int_in(G, "G", 1, 2**31 - 1)
+    G = _args.int_in("sketch", G, "G", 1, 2**31 - 1)
     m, k = _bloom_mk(m, k)
     n = _column(buf, off, gid, "gid", G, check)
     dev = buf.device
@@ -244,14 +217,11 @@ def bloom_bits(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: int, 
     off, gid = off.contiguous(), gid.contiguous()
     ptr = _native.ptr
     if buf.is_cuda:
-        buf = _pad16(buf.contiguous())
-        rc = _native.hip().hm_bloom_add(ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits),
-                                        _native.stream_of(dev))
-        _native.check(rc, "hm_bloom_add")
+        buf = _args.pad16(buf.contiguous())
+        _native.call_hip("hm_bloom_add", dev, ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits))
     else:
         buf = _host_buf(buf.contiguous())
-        _host_rc(_native.host().hm_bloom_add_cpu(ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits)),
-                 "hm_bloom_add_cpu")
+        _native.call_host("hm_bloom_add", ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits))
     return bits
 
 
@@ -259,7 +229,7 @@ def bloom_test(bits: torch.Tensor, fid: torch.Tensor, buf: torch.Tensor, off: to
                check: bool = True) -> torch.Tensor:
     """uint8 ``[n]``: 1 when all ``k`` bits of key ``s`` are set in filter ``fid[s]`` of ``bits``
     (uint8 ``[F, m / 8]``)."""
-    _want(bits, "bits", torch.uint8, 2)
+    _args.want("sketch", bits, "bits", torch.uint8, 2)
     F = bits.shape[0]
     if F < 1 or F > 2**31 - 1:
         raise ValueError(f"sketch: bits must hold at least one filter, got shape {tuple(bits.shape)}")
@@ -277,14 +247,11 @@ def bloom_test(bits: torch.Tensor, fid: torch.Tensor, buf: torch.Tensor, off: to
     off, fid = off.contiguous(), fid.contiguous()
     ptr = _native.ptr
     if buf.is_cuda:
-        buf = _pad16(buf.contiguous())
-        rc = _native.hip().hm_bloom_test(ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit),
-                                         _native.stream_of(dev))
-        _native.check(rc, "hm_bloom_test")
+        buf = _args.pad16(buf.contiguous())
+        _native.call_hip("hm_bloom_test", dev, ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit))
     else:
         buf = _host_buf(buf.contiguous())
-        _host_rc(_native.host().hm_bloom_test_cpu(ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k,
-                                                  ptr(hit)), "hm_bloom_test_cpu")
+        _native.call_host("hm_bloom_test", ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit))
     return hit
 
 

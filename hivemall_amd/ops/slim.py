@@ -23,6 +23,7 @@ import ctypes as C
 import torch
 
 from .. import _native
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -35,28 +36,13 @@ _native.register_host("hm_slim_cd_cpu", [_P, _P, _I64, C.c_int, _F64, _F64, C.c_
 KMAX = 128          # neighbours per item of slim_cd (an fp64 K x K Gram matrix in one CU's LDS)
 
 
-def _want(t, name: str, dtype, ndim: int) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"slim: {name} must be a torch tensor, got {type(t).__name__}")
-    if t.dtype != dtype:
-        raise ValueError(f"slim: {name} must be {dtype}, got {t.dtype}")
-    if t.dim() != ndim:
-        raise ValueError(f"slim: {name} must have {ndim} dimension(s), got shape {tuple(t.shape)}")
-
-
-def _same_device(ts, names) -> None:
-    for t, nm in zip(ts[1:], names[1:]):
-        if t.device != ts[0].device:
-            raise ValueError(f"slim: {nm} is on {t.device}, {names[0]} on {ts[0].device}")
-
-
 def check_csc(colptr: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor) -> int:
     """Validate a CSC triple (dtypes, shapes, offsets, row ids strictly increasing inside every
     column); returns the number of columns."""
-    _want(colptr, "colptr", torch.int64, 1)
-    _want(rows, "rows", torch.int32, 1)
-    _want(vals, "vals", torch.float64, 1)
-    _same_device((colptr, rows, vals), ("colptr", "rows", "vals"))
+    _args.want("slim", colptr, "colptr", torch.int64, 1)
+    _args.want("slim", rows, "rows", torch.int32, 1)
+    _args.want("slim", vals, "vals", torch.float64, 1)
+    _args.same_device("slim", (colptr, rows, vals), ("colptr", "rows", "vals"))
     nnz = rows.numel()
     if colptr.numel() < 1 or vals.numel() != nnz:
         raise ValueError("slim: colptr must have C + 1 entries and rows / vals the same length")
@@ -79,13 +65,13 @@ def slim_gram(colptr: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor,
 
     ``check=False`` skips the validation of the CSC triple (``check_csc``) for a caller that
     has validated it once and launches many chunks."""
-    _want(target, "target", torch.int32, 1)
-    _want(nbr, "nbr", torch.int32, 2)
+    _args.want("slim", target, "target", torch.int32, 1)
+    _args.want("slim", nbr, "nbr", torch.int32, 2)
     if check:
         n_cols = check_csc(colptr, rows, vals)
     else:
         n_cols = colptr.numel() - 1
-    _same_device((colptr, target, nbr), ("colptr", "target", "nbr"))
+    _args.same_device("slim", (colptr, target, nbr), ("colptr", "target", "nbr"))
     n, K = nbr.shape
     if target.numel() != n:
         raise ValueError(f"slim: target has {target.numel()} entries, nbr {n} rows")
@@ -100,24 +86,20 @@ def slim_gram(colptr: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor,
         return G, b
     colptr, rows, vals, target, nbr = (t.contiguous() for t in (colptr, rows, vals, target, nbr))
     p = _native.ptr
+    args = (p(colptr), p(rows), p(vals), n_cols, p(target), p(nbr), n, K, p(G), p(b))
     if colptr.is_cuda:
-        rc = _native.hip().hm_slim_gram(p(colptr), p(rows), p(vals), n_cols, p(target), p(nbr), n, K,
-                                        p(G), p(b), _native.stream_of(dev))
-        _native.check(rc, "hm_slim_gram")
+        _native.call_hip("hm_slim_gram", dev, *args)
     else:
-        rc = _native.host().hm_slim_gram_cpu(p(colptr), p(rows), p(vals), n_cols, p(target), p(nbr),
-                                             n, K, p(G), p(b))
-        if rc != 0:
-            raise RuntimeError(f"hm_slim_gram_cpu failed: {rc}")
+        _native.call_host("hm_slim_gram", *args)
     return G, b
 
 
 def slim_cd(G: torch.Tensor, b: torch.Tensor, l1: float, l2: float, iters: int,
             eps: float) -> torch.Tensor:
     """W fp64 [n, K] from G fp64 [n, K, K] and b fp64 [n, K]; K <= ``KMAX``."""
-    _want(G, "G", torch.float64, 3)
-    _want(b, "b", torch.float64, 2)
-    _same_device((G, b), ("G", "b"))
+    _args.want("slim", G, "G", torch.float64, 3)
+    _args.want("slim", b, "b", torch.float64, 2)
+    _args.same_device("slim", (G, b), ("G", "b"))
     n, K = b.shape
     if tuple(G.shape) != (n, K, K):
         raise ValueError(f"slim: G must be [n, K, K] for b [n, K], got {tuple(G.shape)} and {tuple(b.shape)}")
@@ -130,13 +112,9 @@ def slim_cd(G: torch.Tensor, b: torch.Tensor, l1: float, l2: float, iters: int,
         return W
     G, b = G.contiguous(), b.contiguous()
     p = _native.ptr
+    args = (p(G), p(b), n, K, float(l1), float(l2), int(iters), float(eps), p(W))
     if G.is_cuda:
-        rc = _native.hip().hm_slim_cd(p(G), p(b), n, K, float(l1), float(l2), int(iters), float(eps),
-                                      p(W), _native.stream_of(G.device))
-        _native.check(rc, "hm_slim_cd")
+        _native.call_hip("hm_slim_cd", G.device, *args)
     else:
-        rc = _native.host().hm_slim_cd_cpu(p(G), p(b), n, K, float(l1), float(l2), int(iters),
-                                           float(eps), p(W))
-        if rc != 0:
-            raise RuntimeError(f"hm_slim_cd_cpu failed: {rc}")
+        _native.call_host("hm_slim_cd", *args)
     return W

@@ -19,11 +19,11 @@ the OpenMP twin.
 from __future__ import annotations
 
 import ctypes as C
-import operator
 
 import torch
 
 from .. import _native
+from . import _args
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -32,19 +32,6 @@ _native.register_host("hm_sst_scores_cpu", [_P, _I64, _I64] + [C.c_int] * 6 + [_
 
 DIM_MAX = 64        # rows = one wave; three 64 x 64 fp64 matrices are 96 KiB of LDS
 SWEEP_CAP = 30
-
-
-def _int_in(v, name: str, lo: int, hi: int | None) -> int:
-    rng = f"{lo}..{hi}" if hi is not None else f">= {lo}"
-    try:
-        if isinstance(v, bool):
-            raise TypeError
-        v = operator.index(v)
-    except TypeError:
-        raise ValueError(f"sst: {name} must be an int {rng}, got {v!r}") from None
-    if v < lo or (hi is not None and v > hi) or abs(v) > 2**31 - 1:
-        raise ValueError(f"sst: {name} must be {rng}, got {v}")
-    return v
 
 
 def supports(w: int, n: int, m: int, g: int, r: int, k: int) -> bool:
@@ -66,39 +53,31 @@ def sst_scores(x: torch.Tensor, w: int = 30, n: int | None = None, m: int | None
         raise ValueError(f"sst: x must be {torch.float64}, got {x.dtype}")
     if x.dim() not in (1, 2):
         raise ValueError(f"sst: x must be [N] or [S, N], got shape {tuple(x.shape)}")
-    w = _int_in(w, "w", 2, DIM_MAX)
-    n = w if n is None else _int_in(n, "n", 1, DIM_MAX)
-    m = w if m is None else _int_in(m, "m", 1, DIM_MAX)
-    g = -w if g is None else _int_in(g, "g", -(2**31 - 1), None)
-    r = _int_in(r, "r", 1, None)
-    k = _int_in(k, "k", 1, None)
+    w = _args.int_in("sst", w, "w", 2, DIM_MAX)
+    n = w if n is None else _args.int_in("sst", n, "n", 1, DIM_MAX)
+    m = w if m is None else _args.int_in("sst", m, "m", 1, DIM_MAX)
+    g = -w if g is None else _args.int_in("sst", g, "g", -(2**31 - 1))
+    r = _args.int_in("sst", r, "r", 1)
+    k = _args.int_in("sst", k, "k", 1)
     if g > m:
         raise ValueError(f"sst: g must be <= m = {m} (the past windows would reach beyond t), got {g}")
     xs = (x if x.dim() == 2 else x[None]).contiguous()
     S, N = xs.shape
-    bad = ~torch.isfinite(xs)
-    if bool(bad.any()):
-        at = int(torch.nonzero(bad.reshape(-1))[0])
-        where = at if x.dim() == 1 else (at // N, at % N)
-        raise ValueError(f"sst: x[{where}] is not finite ({float(xs.reshape(-1)[at])})")
+    where = (lambda at: at) if x.dim() == 1 else (lambda at: (at // N, at % N))
+    _args.all_finite("sst", xs, where)
     need = w + n + max(0, -g) + m
     out = torch.zeros((S, N), dtype=torch.float64, device=x.device)
     sweeps = torch.zeros((S, N), dtype=torch.int32, device=x.device)
     if S and N >= need:
-        p = _native.ptr
+        args = (_native.ptr(xs), S, N, w, n, m, g, r, k, _native.ptr(out), _native.ptr(sweeps))
         if x.is_cuda:
-            rc = _native.hip().hm_sst_scores(p(xs), S, N, w, n, m, g, r, k, p(out), p(sweeps),
-                                             _native.stream_of(x.device))
-            _native.check(rc, "hm_sst_scores")
+            _native.call_hip("hm_sst_scores", x.device, *args)
         else:
-            rc = _native.host().hm_sst_scores_cpu(p(xs), S, N, w, n, m, g, r, k, p(out), p(sweeps))
-            if rc != 0:
-                raise RuntimeError(f"hm_sst_scores_cpu failed: {rc}")
+            _native.call_host("hm_sst_scores", *args)
         capped = sweeps > SWEEP_CAP
         if bool(capped.any()):
             at = int(torch.nonzero(capped.reshape(-1))[0])
-            where = at if x.dim() == 1 else (at // N, at % N)
-            raise RuntimeError(f"sst: the Jacobi SVD of point {where} did not converge in "
+            raise RuntimeError(f"sst: the Jacobi SVD of point {where(at)} did not converge in "
                                f"{SWEEP_CAP} sweeps")
     out, sweeps = out.reshape(x.shape), sweeps.reshape(x.shape)
     return (out, sweeps) if return_sweeps else out

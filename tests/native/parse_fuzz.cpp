@@ -6,8 +6,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#define __device__
-#define __forceinline__ inline
 #include "../../csrc/kernels/parse.h"
 
 int main() {
