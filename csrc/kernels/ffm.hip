@@ -87,7 +87,7 @@ struct FFMParams {
     int lin_atomic;
     const int32_t* hidx;           // lin_atomic 4: hot index of each feature (-1: cold), [num_features]
     const int32_t* hot_id;         // lin_atomic 4: feature of each hot index, [nhot]
-    float* hacc;                   // lin_atomic 4: {z, n, 0, 0} per hot index, [nhot][HACC_STRIDE]
+    float* hacc;                   // lin_atomic 4: ACC {z, n} [nhot], then READ {z, n, 0, 0} [nhot] (HD_SIZE below)
     int nhot;                      // <= HD_SIZE
     int hacc_on;                   // set by the dispatch for a launch that uses the side table
     // Global-bias FTRL state sharded over bias_s 128-B lines during a training launch (sg32 /
@@ -156,19 +156,63 @@ __device__ __forceinline__ void bias_update_sh(const FFMParams& P, float g, floa
 }
 
 // lin_atomic 4 (template LT of the pipelined kernels): the linear FTRL state (z, n) of the
-// P.nhot hot features lives in a dense side table P.hacc[h] = {z, n, 0, 0} (h = P.hidx[feature],
-// -1: cold) for the duration of a launch (ffm_hacc_kernel copies it out of / back into the
-// records around the launch).  A block sums its rows' steps of hot features in LDS, s_hd[h], and
-// adds them to P.hacc by float atomics when it ends; a row reads hacc[h] (DMA'd one row ahead,
-// like the record) plus the block's own sums.  Nothing is lost to a concurrent row, and the
+// P.nhot hot features lives in a dense side table in P.hacc (h = P.hidx[feature], -1: cold) for
+// the duration of a launch (ffm_hacc_kernel copies it out of / back into the records around the
+// launch).  A block sums its rows' steps of hot features in LDS, s_hd[h], and adds them to the
+// table by float atomics when it ends; a row reads entry h (DMA'd one row ahead, like the record)
+// plus the block's own sums.  Nothing is lost to a concurrent row, and the
 // atomics land in the side table, not in the hot features' blocks: atomics on the records
 // themselves drop those lines from L2, which every row reads (per-row atomics on the records: 8.7 M
 // rows/s, block sums flushed onto the records: 28 M, vs 93 M with plain stores;
 // profiles/r6/linhot/).  Cold features keep the plain record stores.
+//
+// The side table is two tables in the one allocation P.hacc (round 9):
+//   ACC  = P.hacc, nhot entries {z, n} of 8 B, contiguous: the only target of the flush atomics, and
+//          the only place a flushed step lives (ffm_hacc_kernel folds ACC back into the records).
+//   READ = P.hacc + hacc_read_off(nhot), nhot entries {z, n, 0, 0} of 16 B: what the rows DMA.
+//          Nothing ever adds to it atomically.
+// Every block copies ACC to READ before its first row (hacc_publish).  Why that is enough:
+//  - plain stores keep the line in the storing XCD's L2, so a block's publish is visible to every
+//    row on its XCD at once, and the rows' READ DMAs are L2 hits that no atomic ever drops (a float
+//    atomic executes at the memory side and drops its line from the XCD's L2: with one table, each
+//    flush sent the rows of its XCD back to memory for the lines it had touched);
+//  - the L2s are not coherent with each other inside a launch, so each XCD keeps its own copy of
+//    READ, refreshed by its own blocks' starts: 64 resident fp32 blocks per XCD at about 0.73 ms each
+//    at the bench shape, one refresh per ~11 us;
+//  - a block starts right after a block on the same CU ended, whose flush dropped the ACC lines it
+//    touched from this XCD's L2 (16 entries per line: nearly every block touches every line), so
+//    the publish reads ACC from the memory side (its loads bypass the CU's L1);
+//  - with one table a reader saw the other blocks' steps only after a local atomic on that very
+//    entry dropped its line, or after eviction: the READ view is no staler than that;
+//  - no step can be lost: sums live only in ACC, which only the atomics and dir 1 touch.
+// A READ value that mixes two publishes, or lags one, is one more stale read of a Hogwild learner.
+// The one-entry-per-line layout (16-B entries, 8 to a line: 73.6 vs 76.0 M rows/s in round 6) was
+// there because the atomics landed on the lines the rows read; they no longer do.  ACC dense makes
+// each flush wave-instruction 256 contiguous bytes, the shape float atomics run at full rate in
+// (one entry per line: 32 lines of 8 B each per instruction).
 constexpr int HD_SIZE = 2048;
 constexpr int HD12_SIZE = 1024;   // ffm_pipe_sg12_kernel (bf16 12-B slots)
-// one side-table entry per 128-B line (16-B entries, 8 to a line: 73.6 vs 76.0 M rows/s)
-constexpr int HACC_STRIDE = 32;
+// floats between READ entries: contiguous (90.6-90.7 M rows/s; one entry per line, as the single
+// table had them, 89.9-90.0 M: docs/perf_notes.md round 9)
+constexpr int HACC_READ_STRIDE = 4;
+// READ's offset in P.hacc, in floats: behind ACC's 2 nhot, on a 128-B line (hivemall_amd/ops/ffm.py
+// _lin_hot_tables allocates by the same rule)
+__host__ __device__ __forceinline__ int hacc_read_off(int nhot) { return (2 * nhot + 31) & ~31; }
+
+// ACC -> READ, by every thread of a block before its first row: coalesced loads that bypass the
+// CU's L1 (an earlier block's publish may have left the lines there), plain 16-B stores.
+template <int TPB>
+__device__ __forceinline__ void hacc_publish(float* __restrict__ hacc, int nhot, int tid) {
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    float4* rd = reinterpret_cast<float4*>(hacc + hacc_read_off(nhot));
+    // two entries per 16-B load (ACC is allocated in whole lines: the pair of an odd nhot's last
+    // entry is inside it)
+    for (int t = 2 * tid; t < nhot; t += 2 * TPB) {
+        const f4v a = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(hacc) + (t >> 1));
+        rd[(HACC_READ_STRIDE / 4) * t] = make_float4(a.x, a.y, 0.f, 0.f);
+        if (t + 1 < nhot) rd[(HACC_READ_STRIDE / 4) * (t + 1)] = make_float4(a.z, a.w, 0.f, 0.f);
+    }
+}
 // default grid of a side-table launch: a block's sums are flushed when it ends, so fewer, longer-
 // lived blocks add fewer atomics per row (distinct hot features per block grow slower than its
 // rows).  Measured (profiles/r6/linhot/): 8,192 blocks 76.0 M rows/s, 4,096 82.4 M (+0.90e-3),
@@ -1122,6 +1166,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
         for (int t = tid; t < HD_SIZE; t += TPB) s_hd[t] = make_float2(0.f, 0.f);
     }
     int nh = -1, kh = -1;            // LT, W_LIN lanes: hot index of the next / current row's feature
+    const float* hread = LT ? P.hacc + hacc_read_off(P.nhot) : nullptr;   // the rows' READ table
 
     // slot s = tid + j TPB is (a, b) = (s / F, s % F); slots past F F are (0, 0).  CFG 0 keeps
     // a | b << 8.  SPEC keeps a << 4 | b << 10 | t << 16: the byte offsets of s_m[][a], s_m[][b]
@@ -1263,7 +1308,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
             if (c_lpack) {
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin4[bf][0], 16, 0, 0);
                 if constexpr (LT != 0)   // every lane: the wave's DMA count stays exact
-                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(P.hacc + HACC_STRIDE * max(nh, 0)), (lds_ptr_t)&s_hacc[bf][0], 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(hread + HACC_READ_STRIDE * max(nh, 0)), (lds_ptr_t)&s_hacc[bf][0], 16, 0, 0);
                 return;
             }
             __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin[bf][0][0], 4, 0, 0);
@@ -1278,6 +1323,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     if (row >= P.B) return;
     if (tid == 0) { s_bcur[0] = 0.f; s_bcur[1] = 0.f; }
     dma_meta(0, row);
+    if constexpr (LT != 0) {
+        if (c_hacc) hacc_publish<TPB>(P.hacc, P.nhot, tid);   // ACC -> READ (HD_SIZE above)
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);
     bar_raw();
     publish_meta(0);
@@ -1575,12 +1623,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
         // are published by the barrier).  No-return atomics, not waited for: a wait here for their
         // completion under every block's contention cost 89 -> 68 M rows/s (profiles/r6/linhot/)
         bar_raw();
-        // Lanes 2e, 2e + 1 add z, n of entry e (one 8-B run per entry and instruction: 67 -> 76 M
-        // rows/s against one lane adding both)
+        // Thread t adds z (t even) or n (t odd) of entry t / 2 to ACC[t]: every wave-instruction
+        // covers 256 contiguous bytes.  The non-zero test keeps a -0.0 entry bit-exact; a masked lane
+        // does not widen the instruction's span.
         if (c_hacc)
             for (int t = tid; t < 2 * P.nhot; t += TPB) {
                 const float2 d = s_hd[t >> 1];
-                if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + HACC_STRIDE * (t >> 1) + (t & 1), (t & 1) ? d.y : d.x);
+                if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + t, (t & 1) ? d.y : d.x);
             }
     }
 #undef SA
@@ -1640,6 +1689,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
         for (int t = tid; t < HD12_SIZE; t += 256) s_hd[t] = make_float2(0.f, 0.f);
     }
     int nh = -1, kh = -1;            // LT, W_LIN lanes: hot index of the next / current row's feature
+    const float* hread = LT ? P.hacc + hacc_read_off(P.nhot) : nullptr;   // the rows' READ table
     // linear records inside the blocks (the first 16-B chunk after the 12-B slots), whether they
     // are accessed as one 16-B record (lpack) or as three 4-B words: the tail zeroing skips them
     const bool lin_in_tail = reinterpret_cast<const char*>(w) == vb + (size_t)P.vpad * 12;
@@ -1721,7 +1771,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
             if (i >= 0 && P.lpack) {
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin4[bf][0], 16, 0, 0);
                 if (LT && nh >= 0)
-                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(P.hacc + HACC_STRIDE * nh), (lds_ptr_t)&s_hacc[bf][0], 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((glb_ptr_t)(hread + HACC_READ_STRIDE * nh), (lds_ptr_t)&s_hacc[bf][0], 16, 0, 0);
             } else if (i >= 0) {
                 __builtin_amdgcn_global_load_lds((glb_ptr_t)&LW(w, i), (lds_ptr_t)&s_lin[bf][0][0], 4, 0, 0);
                 if (P.train) {
@@ -1736,6 +1786,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     if (row >= P.B) return;
     if (tid == 0) { s_bcur[0] = 0.f; s_bcur[1] = 0.f; }
     dma_meta(0, row);
+    if constexpr (LT != 0) {
+        if (P.hacc_on) hacc_publish<256>(P.hacc, P.nhot, tid);   // (as in ffm_pipe_sg32_kernel)
+    }
     __builtin_amdgcn_s_waitcnt(0x0F70);
     bar_raw();
     publish_meta(0);
@@ -1959,7 +2012,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
         if (P.hacc_on)
             for (int t = tid; t < 2 * P.nhot; t += 256) {
                 const float2 d = s_hd[t >> 1];
-                if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + HACC_STRIDE * (t >> 1) + (t & 1), (t & 1) ? d.y : d.x);
+                if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + t, (t & 1) ? d.y : d.x);
             }
     }
 #undef SA
@@ -2030,18 +2083,20 @@ int dispatch_lean(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t st
     HM_LAUNCH_RET();
 }
 
-// lin_atomic 4: dir 0 copies the hot features' (z, n) from their records into the side table
-// before a launch, dir 1 writes them back (w = f(z, n)) after it.
+// lin_atomic 4: dir 0 copies the hot features' (z, n) from their records into both side tables (ACC
+// and READ, HD_SIZE above)
+// before a launch, dir 1 folds ACC back into the records (w = f(z, n)) after it.
 __global__ __launch_bounds__(256) void ffm_hacc_kernel(FFMParams P, float* __restrict__ w, int dir) {
     const int h = blockIdx.x * 256 + threadIdx.x;
     if (h >= P.nhot) return;
     float4* rp = reinterpret_cast<float4*>(&LW(w, P.hot_id[h]));
-    float4* ap = reinterpret_cast<float4*>(P.hacc + HACC_STRIDE * h);
+    float2* ap = reinterpret_cast<float2*>(P.hacc) + h;
     const float4 r = *rp;
     if (dir == 0) {
-        *ap = make_float4(r.y, r.z, 0.f, 0.f);
+        *ap = make_float2(r.y, r.z);
+        *reinterpret_cast<float4*>(P.hacc + hacc_read_off(P.nhot) + HACC_READ_STRIDE * h) = make_float4(r.y, r.z, 0.f, 0.f);
     } else {
-        const float4 a = *ap;
+        const float2 a = *ap;
         const float nw = a.y > 0.f ? ftrl_weight(a.x, a.y, P.alpha, P.beta, P.lambda1, P.lambda2) : r.x;
         *rp = make_float4(nw, a.x, a.y, r.w);
     }

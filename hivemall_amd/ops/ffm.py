@@ -223,7 +223,12 @@ _LIN_DEFER = int(os.environ.get("HM_FFM_LIN_DEFER", "1") != "0")
 #   4 (default): the top HM_FFM_LIN_HOT features (by frequency in the learner's first batch) keep
 #     (z, n) in a dense side table during a launch; each block sums its rows' steps of them in LDS
 #     and adds the sums by float atomics when it ends; the other features keep plain record stores
-#     (csrc/kernels/ffm.hip ffm_hacc_kernel).
+#     (csrc/kernels/ffm.hip ffm_hacc_kernel).  The table is two tables in one allocation: ACC, 8-B
+#     {z, n} entries, contiguous, the atomics' only target (a flush instruction covers 256
+#     contiguous bytes); and READ, 16-B {z, n, 0, 0} entries on a 128-B line behind it, which the
+#     rows read and every block refreshes from ACC when it starts.  No atomic lands on READ, so
+#     none drops the lines the rows read from L2: that is what the earlier one-entry-per-line
+#     layout of a single table paid for (csrc/kernels/ffm.hip, HD_SIZE).
 #   0: plain record stores (a concurrent row's step to the same feature is lost)
 # Measured and removed: 1 - 3, float atomics on the records themselves (8.7 M rows/s — the atomics
 # drop the hot features' block lines from L2; profiles/r6/linhot/).
@@ -232,13 +237,25 @@ _LIN_DEFER = int(os.environ.get("HM_FFM_LIN_DEFER", "1") != "0")
 LIN_MODES = (0, 4)
 _LIN_ATOMIC = int(os.environ.get("HM_FFM_LIN_ATOMIC", "4"))
 _LIN_HOT_N = min(int(os.environ.get("HM_FFM_LIN_HOT", "2048")), 2048)   # <= HD_SIZE of the kernel
-_LIN_HOT: dict = {}   # (device, w.data_ptr(), NF, H) -> (hidx int32 [NF], hot_id int32 [H], hacc f32 [H, 32], [launches])
+_LIN_HOT: dict = {}   # (device, w.data_ptr(), NF, H) -> (hidx int32 [NF], hot_id int32 [H], hacc f32 (ACC | READ), [launches])
 _LIN_HOT_KEEP = 8     # states whose tables are kept (4 MB index each at 2^20 features); an evicted
                       # state rebuilds its table from its next batch (its records hold the folded
                       # state after every launch, so nothing is lost)
 
 
 _LIN_HOT_REFRESH = int(os.environ.get("HM_FFM_LIN_HOT_REFRESH", "256"))   # launches between rebuilds
+
+
+def _hacc_read_off(nhot: int) -> int:
+    """READ's offset in the side-table allocation, in floats: behind the nhot 8-B entries of ACC, on
+    a 128-B line (hacc_read_off of csrc/kernels/ffm.hip)."""
+    return (2 * nhot + 31) & ~31
+
+
+def _hacc_views(hacc: torch.Tensor, nhot: int):
+    """(ACC [nhot, 2], READ [nhot, 4]) of a side-table allocation: {z, n} and {z, n, 0, 0}."""
+    off = _hacc_read_off(nhot)
+    return hacc[:2 * nhot].view(nhot, 2), hacc[off:off + 4 * nhot].view(nhot, 4)
 
 
 def _lin_hot_tables(state: dict, idx: torch.Tensor, nhot: int):
@@ -261,7 +278,8 @@ def _lin_hot_tables(state: dict, idx: torch.Tensor, nhot: int):
         top = top[cnt[top] > 0].to(torch.int32)
         hidx = torch.full((nf,), -1, dtype=torch.int32, device=w.device)
         hidx[top.long()] = torch.arange(top.numel(), dtype=torch.int32, device=w.device)
-        hacc = torch.zeros(max(1, top.numel()), 32, dtype=torch.float32, device=w.device)  # HACC_STRIDE
+        n = max(1, top.numel())
+        hacc = torch.zeros(_hacc_read_off(n) + 4 * n, dtype=torch.float32, device=w.device)
         while len(_LIN_HOT) >= _LIN_HOT_KEEP:        # the oldest states' tables go first
             _LIN_HOT.pop(next(iter(_LIN_HOT)))
         t = _LIN_HOT[key] = (hidx, top, hacc, [0])
@@ -394,7 +412,7 @@ def ffm_step(state: dict, idx: torch.Tensor, fld: torch.Tensor | None, val: torc
         hidx = hot_id = hacc = None
         if lin_mode == 4 and train and hyper.use_linear and _lin_addressing(state)[1]:
             # the bf16 kernel's LDS holds the sums of 1,024 hot features (HD12_SIZE)
-            hidx, hot_id, hacc = _lin_hot_tables(state, idx, 1024 if bf16 else _LIN_HOT_N)
+            hidx, hot_id, hacc = _lin_hot_tables(state, idx, min(1024, _LIN_HOT_N) if bf16 else _LIN_HOT_N)
         nhot = hot_id.numel() if hot_id is not None else 0
         ip[26], ip[27] = lin_mode if nhot else 0, nhot     # no hot feature: plain record stores
         # aux[0] is reserved.  aux[1]: multi-hot rows (a repeated field or feature) are deferred by the
