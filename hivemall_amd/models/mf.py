@@ -132,6 +132,11 @@ def _dev(x, dtype, dev) -> torch.Tensor:
     return torch.as_tensor(np.asarray(x, dtype=torch.empty(0, dtype=dtype).numpy().dtype)).to(dev)
 
 
+def _in_range(ids: torch.Tensor, n: int) -> torch.Tensor:
+    """Mask of the ids inside a table of ``n`` rows (the engines skip a row naming any other)."""
+    return (ids >= 0) & (ids < n)
+
+
 class _MFBase(Learner):
     SQL_DP = "shard"
     def mix(self) -> None:
@@ -295,9 +300,12 @@ class MatrixFactorization(_MFBase):
                 mu = self.dp_sum(float(r.double().sum().item())) / max(
                     1.0, self.dp_sum(float(r.numel())))
                 self.state["mu"].fill_(mu)
-        self.seen_u[u.long()] = True
-        self.seen_i[i.long()] = True
-        loss = torch.empty(u.numel(), device=dev)
+        # rows naming an id outside the tables are skipped by both engines: they mark nothing
+        # seen, and their loss slot stays 0 (the engines never write it)
+        ok = _in_range(u, self.n_users) & _in_range(i, self.n_items)
+        self.seen_u[u[ok].long()] = True
+        self.seen_i[i[ok].long()] = True
+        loss = torch.zeros(u.numel(), device=dev)
         for ep in self.epochs(int(self.cl["iters"]), data=(u, i, r)):
             self._step(u, i, r, loss=loss)
             self._epoch_mix(ep)
@@ -313,7 +321,9 @@ class MatrixFactorization(_MFBase):
         dev = self.device
         u = torch.as_tensor(np.asarray(users, dtype=np.int32)).to(dev)
         i = torch.as_tensor(np.asarray(items, dtype=np.int32)).to(dev)
-        out = torch.empty(u.numel(), device=dev)
+        # both engines skip a pair naming an id outside the tables and leave its slot as it is:
+        # mu, the prediction for a pair of which nothing is known
+        out = self.state["mu"].to(dev, torch.float32).repeat(u.numel())
         self._step(u, i, torch.zeros(u.numel(), device=dev), train=False, pred=out)
         return out.cpu().numpy()
 
@@ -532,9 +542,7 @@ class BPRMF(_MFBase):
                 ni = int(self.mixer.all_reduce_scalar(float(ni), "max"))
             self.init_state(nu, ni)
         if self.sharded is not None:
-            self.seen_u[tu.long()] = True
-            self.seen_i[ti.long()] = True
-            self.seen_i[tj.long()] = True
+            self._mark_seen(tu, ti, tj)
             self.no_checkpoint("-shard_model")
             for ep in range(int(self.cl["iters"])):
                 el = self.dp_sum(self._step_sharded(tu, ti, tj))
@@ -547,9 +555,7 @@ class BPRMF(_MFBase):
                 self.seen_u, self.seen_i = f[0] > 0, f[1] > 0
             self.state = self.full_state()
             return self
-        self.seen_u[tu.long()] = True
-        self.seen_i[ti.long()] = True
-        self.seen_i[tj.long()] = True
+        self._mark_seen(tu, ti, tj)
         for ep in self.epochs(int(self.cl["iters"]), data=(tu, ti, tj)):
             el = self.dp_sum(self.step(tu, ti, tj))
             self._epoch_end(el)
@@ -558,6 +564,14 @@ class BPRMF(_MFBase):
                 break
         self.mix()
         return self
+
+    def _mark_seen(self, tu, ti, tj) -> None:
+        """Mark the rows the triples update; a triple naming an id outside the tables is skipped
+        by both engines and marks nothing."""
+        ok = _in_range(tu, self.n_users) & _in_range(ti, self.n_items) & _in_range(tj, self.n_items)
+        self.seen_u[tu[ok].long()] = True
+        self.seen_i[ti[ok].long()] = True
+        self.seen_i[tj[ok].long()] = True
 
     @staticmethod
     def build_csr(users: torch.Tensor, items: torch.Tensor, n_users: int):
