@@ -12,6 +12,7 @@ is what ``train_slim`` needs as its neighbour lists.  ``cosine_knn`` is its SQL 
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -412,10 +413,9 @@ bbit_minhash.batch = _bbit_minhash_udf_batch
 
 
 # ------------------------------------------------------------------ top-k
-@udtf("each_top_k", per_row=False)
-def each_top_k(k, group, score, *cols):
-    """Top-|k| rows by ``score`` within each consecutive ``group`` (k < 0: bottom-k).
-    Output columns: (rank, key(=score), cols...)."""
+def _each_top_k_python(k, group, score, *cols):
+    """The definition of ``each_top_k``: the per-row loop the native engine is checked against and
+    the path of every input the engine declines."""
     import pandas as pd
     kk = int(k[0] if isinstance(k, (list, tuple)) else k)
     rev = kk > 0
@@ -430,6 +430,162 @@ def each_top_k(k, group, score, *cols):
         for r, i in enumerate(idxs, start=1):
             rows.append((r, score[i]) + tuple(c[i] for c in cols))
     return pd.DataFrame(rows, columns=["rank", "key"] + [f"c{i}" for i in range(len(cols))])
+
+
+# The native route: ops/each_top_k.py (the gfx950 kernels, or their OpenMP twin on the CPU) returns
+# the selected row indices in output order, which is all the loop above computes.  It is taken
+# only where the result provably equals the loop's (docs/compat.md "each_top_k engine"); every
+# other input is declined and goes through the loop, with its results and its exceptions.
+EACH_TOP_K_CALLS = {"native": 0, "python": 0}      # how the calls were served (tests assert the route)
+_FP64_EXACT = 2**53
+
+
+def _etk_k(k):
+    """The int the loop reads from its first argument; None where it would raise."""
+    try:
+        return int(k[0] if isinstance(k, (list, tuple)) else k)
+    except Exception:
+        return None
+
+
+def _etk_scores(score):
+    """The score column as fp64 when that loses nothing: a list of Python ints and floats (no
+    bool, None, Decimal, str or NumPy scalar), or a numeric array, with every int inside
+    +-2^53 and no NaN.  None otherwise."""
+    try:
+        if isinstance(score, np.ndarray):
+            if score.ndim != 1 or score.dtype.kind not in "fiu":
+                return None
+            if score.dtype.kind != "f" and score.size and \
+                    (int(score.max()) > _FP64_EXACT or int(score.min()) < -_FP64_EXACT):
+                return None
+            arr = score.astype(np.float64)
+        elif isinstance(score, (list, tuple)):
+            types = set(map(type, score))
+            if not types <= {int, float}:
+                return None
+            if types == {int}:
+                ints = np.array(score, dtype=np.int64)
+                if ints.size and (int(ints.max()) > _FP64_EXACT or int(ints.min()) < -_FP64_EXACT):
+                    return None
+                arr = ints.astype(np.float64)
+            else:
+                if int in types and not all(-_FP64_EXACT <= v <= _FP64_EXACT for v in score if type(v) is int):
+                    return None
+                arr = np.array(score, dtype=np.float64)
+        else:
+            return None
+    except OverflowError:
+        return None
+    return None if np.isnan(arr).any() else arr
+
+
+def _etk_codes(group):
+    """``(codes int32 [n], number of groups)``, groups numbered by first appearance as the loop's
+    dict orders them, for a column of only ``int``, only ``str`` or only finite ``float`` values
+    (or such an array).  None for nulls, NaN and mixed types, whose dict semantics stay the
+    loop's."""
+    import pandas as pd
+
+    if isinstance(group, np.ndarray):
+        if group.ndim != 1 or group.dtype.kind not in "fiuU":
+            return None
+        vals = group
+    elif isinstance(group, (list, tuple)):
+        types = set(map(type, group))
+        if len(types) != 1 or not types <= {int, float, str}:
+            return None
+        t = types.pop()
+        try:
+            vals = np.array(group, dtype=np.int64 if t is int else np.float64 if t is float else object)
+        except OverflowError:
+            return None
+    else:
+        return None
+    if vals.dtype.kind == "f":
+        if not np.isfinite(vals).all():
+            return None
+        vals = vals + 0.0                           # -0.0 and 0.0 are one dict key
+    codes, uniques = pd.factorize(vals)
+    return codes.astype(np.int32), len(uniques)
+
+
+def _each_top_k_native(kk, group, score, device):
+    """``(rows int64 [M], rank int64 [M])`` of ``each_top_k`` from the native engine, or None where
+    it declines."""
+    from ..models.base import resolve_device
+    from ..ops import each_top_k as etk
+
+    if kk is None or kk == 0 or not etk.supports(kk) or os.environ.get("HM_SQL_BATCH_UDTF", "1") == "0":
+        return None
+    try:
+        n = len(group)
+        if len(score) != n:
+            return None
+    except TypeError:
+        return None
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    if n > etk.N_MAX:
+        return None
+    arr = _etk_scores(score)
+    gc = _etk_codes(group) if arr is not None else None
+    if gc is None:
+        return None
+    dev = resolve_device(device)
+    try:
+        from .. import _native
+
+        _native.hip() if dev.type == "cuda" else _native.host()
+    except (RuntimeError, OSError):
+        return None                                 # no native library: the loop serves
+    rows, outptr = etk.segment_topk(torch.from_numpy(arr).to(dev), torch.from_numpy(gc[0]).to(dev), gc[1],
+                                    abs(kk), largest=kk > 0)
+    rows, outptr = rows.cpu().numpy().astype(np.int64), outptr.cpu().numpy()
+    rank = np.arange(1, len(rows) + 1, dtype=np.int64) - np.repeat(outptr[:-1], np.diff(outptr))
+    return rows, rank
+
+
+def each_top_k_batch(k, group, score, device=None):
+    """``(rows int64 [M], rank int64 [M])``: the input row and the rank (from 1) of every output
+    row of ``each_top_k(k, group, score)``, in its output order, for callers that hold columns
+    (lists or NumPy arrays) and gather their own payload.  Runs the native engine on ``device``
+    (default: the GPU when there is one) where it applies and the Python loop's ordering
+    otherwise; the result is the same."""
+    kk = int(k)
+    res = _each_top_k_native(kk, group, score, device)
+    if res is not None:
+        return res
+    order = {}
+    for i in range(len(group)):
+        order.setdefault(group[i], []).append(i)
+    rows, rank = [], []
+    for idxs in order.values():
+        idxs = sorted(idxs, key=lambda i: score[i], reverse=kk > 0)[:abs(kk)]
+        rows.extend(idxs)
+        rank.extend(range(1, len(idxs) + 1))
+    return np.asarray(rows, dtype=np.int64), np.asarray(rank, dtype=np.int64)
+
+
+@udtf("each_top_k", per_row=False)
+def each_top_k(k, group, score, *cols, session=None):
+    """Top-|k| rows by ``score`` within each consecutive ``group`` (k < 0: bottom-k).
+    Output columns: (rank, key(=score), cols...)."""
+    import pandas as pd
+
+    res = _each_top_k_native(_etk_k(k), group, score, _session_device(session))
+    if res is None:
+        EACH_TOP_K_CALLS["python"] += 1
+        return _each_top_k_python(k, group, score, *cols)
+    EACH_TOP_K_CALLS["native"] += 1
+    idx = res[0].tolist()
+    # the loop's own construction (a list of tuples holding the original objects), so the
+    # inferred dtypes are the loop's too
+    data = [res[1].tolist(), [score[i] for i in idx]] + [[c[i] for i in idx] for c in cols]
+    return pd.DataFrame(list(zip(*data)), columns=["rank", "key"] + [f"c{i}" for i in range(len(cols))])
+
+
+each_top_k.wants_session = True
 
 
 def topk_similar(X: torch.Tensor, Y: torch.Tensor | None = None, k: int = 10):
