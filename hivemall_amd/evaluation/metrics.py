@@ -18,6 +18,7 @@ import torch
 
 from ..registry import udaf
 from ..utils.options import Options, UDFArgumentException, opt
+from . import ranking as _ranking
 
 
 def _t(x, dtype=torch.float64) -> torch.Tensor:
@@ -35,6 +36,7 @@ def auc(scores, labels=None, *rest):
       averaged over the group."""
     if labels is not None and len(scores) and isinstance(_first(scores), (list, tuple, np.ndarray)):
         k = rest[0] if rest else None
+        _ranking.RANK_EVAL_CALLS["python"] += 1
         return _mean([ranking_auc(r, g, _first(k) if isinstance(k, (list, tuple)) else k)
                       for r, g in zip(scores, labels)])
     s = _t(scores)
@@ -288,6 +290,7 @@ def ndcg_one(rank, truth, k=None) -> float:
 def _rank_udaf(fn):
     def agg(rank_items, truth, *rest):
         k = _k(rest)
+        _ranking.RANK_EVAL_CALLS["python"] += 1
         return _mean([fn(r, g, k) for r, g in zip(rank_items, truth)])
     return agg
 
@@ -298,3 +301,12 @@ hitrate = udaf("hitrate")(_rank_udaf(hitrate_one))
 mrr = udaf("mrr")(_rank_udaf(mrr_one))
 average_precision = udaf("average_precision")(_rank_udaf(average_precision_one))
 ndcg = udaf("ndcg")(_rank_udaf(ndcg_one))
+
+
+# The column-at-once forms the SQL executor tries first (registry; evaluation/ranking.py): per-row
+# values from the native ranking-measures engine, this module's mean per group.  Direct calls keep
+# the loops above, which are the definition.
+RANK_EVAL_CALLS = _ranking.RANK_EVAL_CALLS
+for _m, _fn in enumerate((precision_at, recall_at, hitrate, mrr, average_precision, ndcg)):
+    _fn.grouped = _ranking.grouped_form(_m)
+auc.grouped = _ranking.grouped_form(6, array_form_only=True)

@@ -12,7 +12,9 @@ registered with a decorator that records its SQL kind:
             groups in, a sequence of ``n_groups`` values out, or None to decline the input.  The
             SQL executor tries it before the per-group loop (``Session._agg_grouped``; not for
             ``DISTINCT``, not with ``HM_SQL_BATCH_UDTF=0``) and falls back to the loop on None;
-            ``approx_count_distinct`` and ``bloom`` have one (``ops/sketch.py``);
+            ``approx_count_distinct`` and ``bloom`` have one (``ops/sketch.py``), and so have the
+            rank measures ``precision_at`` ... ``ndcg`` and ``auc``'s array form
+            (``evaluation/ranking.py``, ``ops/rank_eval.py``);
 * ``udtf``  table function.  ``per_row=True``: ``impl(*args) -> iterable of tuples`` per input
             row (explode-like, usable in ``LATERAL VIEW``).  ``per_row=False``: called once with
             every input row's arguments (``impl(*columns) -> DataFrame``) — the learners.
