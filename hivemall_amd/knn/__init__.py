@@ -8,6 +8,8 @@ matrices followed by ``torch.topk``.  ``topk_similar_csc`` is their sparse sibli
 cosine top-k between the columns of a CSC matrix of any height (``ops/knn_sparse.py``: one
 workgroup per query column, the candidates' dots accumulated in LDS; no dense matrix), which
 is what ``train_slim`` needs as its neighbour lists.  ``cosine_knn`` is its SQL surface.
+``pair_similarity_batch`` / ``pairwise_similarity`` and the ``.batch`` forms of the nine sparse
+similarity / distance functions run whole columns of feature lists on ``ops/pair_sim.py``.
 """
 from __future__ import annotations
 
@@ -410,6 +412,120 @@ def _bbit_minhash_udf_batch(features, num_hashes=128, b=1, session=None, null_fi
 
 minhashes.batch = _minhashes_udf_batch
 bbit_minhash.batch = _bbit_minhash_udf_batch
+
+
+# ------------------------------------------------------------------ pair similarity, column at once
+# The native route of the nine sparse similarity / distance functions above: ops/pair_sim.py (the
+# gfx950 kernel, or its OpenMP twin on the CPU) parses every distinct feature list once with _fv and
+# computes whole columns of pairs.  It is taken only where the result provably equals the
+# functions' (docs/compat.md "Pair-similarity engine"); every other input is declined and goes
+# through them, with their results and their exceptions.  Direct calls on two lists keep their loop.
+PAIR_SIM_CALLS = {"native": 0, "python": 0}        # how the column calls were served (tests assert the route)
+_PAIR_FUNCTIONS = {f.__name__: f for f in (
+    cosine_similarity, cosine_distance, angular_similarity, angular_distance, euclid_distance,
+    euclid_similarity, manhattan_distance, jaccard_similarity, jaccard_distance)}
+
+
+def _pair_function(measure):
+    if measure not in _PAIR_FUNCTIONS:
+        raise ValueError(f"pair_sim: measure must be one of {', '.join(_PAIR_FUNCTIONS)}, got {measure!r}")
+    return _PAIR_FUNCTIONS[measure]
+
+
+def _pair_native(a, b, measure, device):
+    """fp64 [P] tensor of ``measure`` over the rows of two columns (or a column and a constant
+    list) from the engine, or None where it declines."""
+    from ..models.base import resolve_device
+    from ..ops import pair_sim as ps
+
+    if os.environ.get("HM_SQL_BATCH_UDTF", "1") == "0":
+        return None
+    dev = resolve_device(device)
+    enc = ps.encode_columns(a, b, dev)
+    if enc is None:
+        return None
+    lists, ia, ib = enc
+    return ps.pair_measures(lists, torch.from_numpy(ia).to(dev), torch.from_numpy(ib).to(dev), measure,
+                            check=False)                    # the indices were built here
+
+
+def pair_similarity_batch(a, b, measure: str, device=None):
+    """``[measure(x, y) for x, y in zip(a, b)]`` in one native pass: an fp64 tensor on ``device``
+    (default: the GPU when there is one).  ``a`` and ``b`` are columns (a Series or a list of lists
+    of ``"name[:value]"`` strings, None for NULL) of one length, or one of them is a single
+    constant list, the query vector.  ``measure`` is the name of one of the nine functions
+    (``"cosine_similarity"``, ..., ``"jaccard_distance"``).  Inputs the engine declines (dense
+    arrays, maps, non-finite values, ...) are served by the function itself, row by row, and come
+    back as a list."""
+    from ..ops import pair_sim as ps
+
+    fn = _pair_function(measure)
+    res = _pair_native(a, b, measure, device)
+    if res is not None:
+        PAIR_SIM_CALLS["native"] += 1
+        return res
+    PAIR_SIM_CALLS["python"] += 1
+    col_a, col_b = ps._is_column(a), ps._is_column(b)
+    if not (col_a or col_b):
+        raise ValueError("pair_sim: one of a, b must be a column of feature lists")
+    rows_a, rows_b = (_rows_of(a) if col_a else None), (_rows_of(b) if col_b else None)
+    n = len(rows_a if col_a else rows_b)
+    if col_a and col_b and len(rows_b) != n:
+        raise ValueError(f"pair_sim: a holds {n} rows, b {len(rows_b)}")
+    return [fn(rows_a[i] if col_a else a, rows_b[i] if col_b else b) for i in range(n)]
+
+
+def pairwise_similarity(A, B, measure: str, device=None) -> torch.Tensor:
+    """fp64 ``[N, M]`` on ``device``: ``measure(A[i], B[j])`` for every pair of the two columns of
+    feature lists, without materialising the pairs (the cross form of the engine).  Inputs the
+    engine declines are served by the function itself, pair by pair."""
+    from ..models.base import resolve_device
+    from ..ops import pair_sim as ps
+
+    fn = _pair_function(measure)
+    rows_a, rows_b = _rows_of(A), _rows_of(B)
+    dev = resolve_device(device)
+    enc = ps.encode_lists(rows_a + rows_b, dev) if os.environ.get("HM_SQL_BATCH_UDTF", "1") != "0" else None
+    if enc is None:
+        PAIR_SIM_CALLS["python"] += 1
+        vals = [[fn(x, y) for y in rows_b] for x in rows_a]
+        return torch.tensor(vals, dtype=torch.float64).reshape(len(rows_a), len(rows_b)).to(dev)
+    PAIR_SIM_CALLS["native"] += 1
+    lists, index = enc
+    index = torch.from_numpy(index).to(dev)
+    return ps.pair_measures_cross(lists, index[: len(rows_a)].contiguous(), index[len(rows_a):].contiguous(),
+                                  measure, check=False)
+
+
+def _pair_udf_batch(measure: str, extra_args: int = 0):
+    """The column-at-once form of one pair UDF for the SQL executor: a Series, or None (-> the
+    per-row loop) unless one of the two arguments is a column and the engine takes the input.
+    Rows whose first argument is NULL stay NULL (the SQL rule for a NULL first argument); a NULL
+    second argument is the empty list, as in the function."""
+    def batch(a, b, *rest, session=None, null_first=True):
+        import pandas as pd
+
+        if len(rest) > extra_args:
+            return None                                     # the per-row loop raises it
+        res = None
+        if (isinstance(a, pd.Series) or isinstance(b, pd.Series)) and a is not None:
+            res = _pair_native(a, b, measure, _session_device(session))
+        if res is None:
+            PAIR_SIM_CALLS["python"] += 1
+            return None
+        PAIR_SIM_CALLS["native"] += 1
+        if isinstance(a, pd.Series):
+            null = np.fromiter((v is None for v in a.tolist()), dtype=bool, count=len(a))
+        else:
+            null = np.zeros(res.numel(), dtype=bool)
+        return _udf_result(res.cpu().tolist(), null, null_first)
+    return batch
+
+
+for _name, _fn in _PAIR_FUNCTIONS.items():
+    # jaccard_*'s third argument k belongs to the minhash-signature form, which is declined
+    _fn.batch = _pair_udf_batch(_name, extra_args=1 if _name.startswith("jaccard") else 0)
+del _name, _fn
 
 
 # ------------------------------------------------------------------ top-k
