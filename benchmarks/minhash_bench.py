@@ -88,17 +88,13 @@ def composition(buf, off, rowptr, row_of, H):
     """int32 [n_rows, H] from existing parts: hm_mhash per seed, segmented min in torch."""
     import torch
 
-    from hivemall_amd import _native
-    import hivemall_amd.utils.hashing  # noqa: F401  (registers hm_mhash)
+    from hivemall_amd.ops._packed import mhash_packed
 
-    nnz, n_rows = off.numel() - 1, rowptr.numel() - 1
+    n_rows = rowptr.numel() - 1
     flip = -(1 << 31)                                       # unsigned order as signed order
     out = torch.full((H, n_rows), (1 << 31) - 1, dtype=torch.int32, device=buf.device)
-    tmp = torch.empty(nnz, dtype=torch.int32, device=buf.device)
-    p = _native.ptr
     for h in range(H):
-        rc = _native.hip().hm_mhash(p(buf), p(off), nnz, h, 0, p(tmp), _native.stream_of(buf.device))
-        _native.check(rc, "hm_mhash")
+        tmp = mhash_packed(buf, off, 0, h)
         tmp ^= flip
         out[h].scatter_reduce_(0, row_of, tmp, reduce="amin", include_self=True)
     out ^= flip

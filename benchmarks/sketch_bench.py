@@ -98,17 +98,9 @@ def composition(buf, off, gid64, G, p):
     """(reg uint8 [G, 2^p], hist int32 [G, 66]) from existing parts."""
     import torch
 
-    from hivemall_amd import _native
-    import hivemall_amd.utils.hashing  # noqa: F401  (registers hm_mhash)
+    from hivemall_amd.ops._packed import mhash_packed
 
-    n = off.numel() - 1
-    ptr = _native.ptr
-    halves = []
-    for seed in (0x9747B28C, 0x5BD1E995):
-        t = torch.empty(n, dtype=torch.int32, device=buf.device)
-        _native.check(_native.hip().hm_mhash(ptr(buf), ptr(off), n, seed, 0, ptr(t),
-                                             _native.stream_of(buf.device)), "hm_mhash")
-        halves.append(t.long() & 0xFFFFFFFF)
+    halves = [mhash_packed(buf, off, 0, seed).long() & 0xFFFFFFFF for seed in (0x9747B28C, 0x5BD1E995)]
     h = (halves[0] << 32) | halves[1]                       # int64 bit pattern of h64
     m = 1 << p
     idx = (h >> (64 - p)) & (m - 1)
@@ -142,7 +134,7 @@ def main():
     import torch
 
     from hivemall_amd import misc
-    from hivemall_amd.ops import _args, sketch as sk
+    from hivemall_amd.ops import _packed, sketch as sk
 
     if not a.cpu_only and not torch.cuda.is_available():
         raise SystemExit("sketch_bench: no GPU")
@@ -160,7 +152,7 @@ def main():
     if not a.cpu_only:
         dev = torch.device("cuda")
         sync = lambda: torch.cuda.synchronize(dev)          # noqa: E731
-        buf, off = _args.pad16(buf_h.to(dev)), off_h.to(dev)
+        buf, off = _packed.pad16(buf_h.to(dev)), off_h.to(dev)
         for G, p in HLL_ROWS:
             gid = gids_h[G].to(dev)
             gid64 = gid.long()

@@ -10,11 +10,11 @@
 // Shape.  A 256-thread workgroup owns MH_ROWS consecutive rows (grid stride), i.e. one contiguous
 // span of strings and of bytes.  It walks that span in passes of at most MH_FEATS strings whose
 // bytes fit the MH_BYTES window:
-//   1. the bytes are copied to LDS with aligned 16-B loads (the LDS image keeps the global
-//      address modulo 16, so the stores are aligned 16-B stores too);
+//   1. the bytes are copied to LDS (hm::stage_span of strspan.h, which states what it asks of
+//      buf);
 //   2. one thread per string does the seed-independent half of Murmur3 once: every 4-byte word
-//      k1 -> rotl(k1 * c1, 15) * c2, and the same for the tail word, written to LDS next to the
-//      string's length, its word offset and its local row;
+//      (hm::LdsWords) k1 -> rotl(k1 * c1, 15) * c2, and the same for the tail word, written to
+//      LDS next to the string's length, its word offset and its local row;
 //   3. every thread owns one hash index h of one of S = 256 / H "slots" (H <= 256; S = 1 and
 //      several hash passes of MH_HASHES above that), walks the strings slot, slot + S, ... and
 //      runs only the h1 chain and the final mix.  Lanes of one slot read the same premixed word
@@ -26,6 +26,7 @@
 // simply takes more passes.  The table is written out with coalesced vector stores.
 #include "common.h"
 #include "murmur3.h"
+#include "strspan.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ nlen, const int64_t* __restrict__ rowptr, int64_t n_rows,
         int H, uint32_t seed0, int32_t* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_raw[MH_BYTES + 16];
+    __shared__ uint4 s_raw[hm::stage_vecs(MH_BYTES)];
     __shared__ uint32_t s_words[(MH_BYTES + 16) / 4 + 1];
     __shared__ int32_t s_wbeg[MH_FEATS];     // first premixed word, -1: hash from global memory
     __shared__ int32_t s_len[MH_FEATS];
@@ -88,13 +89,8 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
                 const int nf = fit > 0 ? fit : 1;      // a first string beyond the window goes alone
                 const int64_t pe = p + nf;
                 const int staged = s_end[nf - 1];      // bytes of the pass, at most the window
-                // ---- 1. bytes -> LDS, aligned 16-B chunks; byte i of the span is s_raw[lead + i]
-                const uint8_t* g0 = buf + span0;
-                const int lead = (int)(reinterpret_cast<uintptr_t>(g0) & 15);
-                const int nvec = (lead + staged + 15) >> 4;
-                const uint4* gv = reinterpret_cast<const uint4*>(g0 - lead);
-                for (int v = t; v < nvec; v += MH_THREADS)
-                    reinterpret_cast<uint4*>(s_raw)[v] = gv[v];
+                // ---- 1. bytes -> LDS; byte i of the span is byte lead + i of s_raw
+                const int lead = hm::stage_span<MH_THREADS>(buf + span0, staged, s_raw);
                 __syncthreads();
                 // ---- 2. the seed-independent half, one thread per string
                 if (t < nf) {
@@ -110,14 +106,11 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
                     s_row[t] = lo;
                     s_len[t] = L;
                     if ((int64_t)b + L <= staged) {
-                        const uint8_t* q = s_raw + lead + b;
-                        const int w0 = (lead + b + 3) >> 2, nw = L >> 2;
-                        for (int i = 0; i < nw; ++i) {
-                            const uint32_t k1 = (uint32_t)q[4 * i] | ((uint32_t)q[4 * i + 1] << 8) |
-                                                ((uint32_t)q[4 * i + 2] << 16) | ((uint32_t)q[4 * i + 3] << 24);
-                            s_words[w0 + i] = hm::mm_premix(k1);
-                        }
-                        s_tail[t] = hm::mm_premix(hm::mm_tail_word(q + nw * 4, L & 3));   // 0 when no tail
+                        const int a = lead + b;
+                        const hm::LdsWords word{reinterpret_cast<const uint32_t*>(s_raw) + (a >> 2), 8 * (a & 3)};
+                        const int w0 = (a + 3) >> 2, nw = L >> 2, r = L & 3;
+                        for (int i = 0; i < nw; ++i) s_words[w0 + i] = hm::mm_premix(word(i));
+                        s_tail[t] = r ? hm::mm_premix(word(nw) & ((1u << (8 * r)) - 1u)) : 0;
                         s_wbeg[t] = w0;
                     } else {
                         s_tail[t] = 0;
@@ -145,8 +138,7 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
                             for (int i = 0; i < nw; ++i) h1 = hm::mm_chain(h1, s_words[w0 + i]);
                             h1 = hm::mm_fmix(h1 ^ s_tail[j], (uint32_t)L);
                         } else {
-                            const uint8_t* q = buf + off[p + j];
-                            h1 = hm::murmur3([&](int i) { return q[i]; }, L, seed);
+                            h1 = hm::mm3(hm::GlobalWords{buf + off[p + j], L}, L, seed);
                         }
                         cur = h1 < cur ? h1 : cur;
                     }
@@ -169,8 +161,7 @@ __global__ __launch_bounds__(MH_THREADS) void minhash_kernel(
 
 }  // namespace
 
-// sig int32 [n_rows, H] (uint32 bit patterns).  buf must be readable in whole aligned 16-B
-// chunks around every staged span (ops/minhash.py pads it).
+// sig int32 [n_rows, H] (uint32 bit patterns)
 HM_API int hm_minhash_sig(const uint8_t* buf, const int64_t* off, const int32_t* nlen,
                           const int64_t* rowptr, int64_t n_rows, int H, uint32_t seed0,
                           int32_t* out, hipStream_t stream) {

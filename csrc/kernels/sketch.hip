@@ -17,16 +17,13 @@
 // schedule: bit-exact with csrc/host/sketch_cpu.cpp and with the Python classes.
 //
 // Input: buf uint8 + off int64 [n + 1] (value s = buf[off[s] .. off[s + 1])) and one int32 group
-// (filter) id per value, unsorted.  buf is readable in whole aligned 16-B chunks (ops/sketch.py
-// pads it).
+// (filter) id per value, unsorted.
 //
-// Front end, shared by the four kernels.  A 256-thread workgroup owns SK_STRINGS consecutive
-// values (grid stride): one contiguous span of bytes, whose first SK_BYTES it copies to LDS with
-// aligned 16-B loads (the LDS image keeps the global address modulo 16).  Each lane then hashes
-// its own value from LDS, one aligned dword pair per 4-byte word; a value that ends beyond the
-// window is hashed from global memory instead.  HyperLogLog does the seed-independent premix
-// rotl(k * c1, 15) * c2 once per word and runs the two seed chains over it; Bloom's second seed
-// is the first hash, so it walks the words twice.
+// Front end, shared by the four kernels: hm::sweep of strspan.h (which states what it asks of
+// buf), SK_STRINGS values and an SK_BYTES window per 256-thread workgroup and step; each lane
+// hashes its own value.  HyperLogLog does the seed-independent premix rotl(k * c1, 15) * c2 once
+// per word and runs the two seed chains over it; Bloom's second seed is the first hash, so it
+// walks the words twice.
 //
 // HyperLogLog update.  The byte maximum is a read filter (stop when the byte is already >= rho)
 // plus a 32-bit compare-and-swap loop on the containing word.  A stale read (this CU's L1,
@@ -42,6 +39,7 @@
 // Bloom add is atomicOr behind the same kind of filter (a stale read can only miss a set bit).
 #include "common.h"
 #include "murmur3.h"
+#include "strspan.h"
 
 namespace {
 
@@ -52,36 +50,6 @@ constexpr int SK_LDS_REG_BYTES = 64 * 1024;  // largest register file kept in LD
 constexpr int SK_MAX_GRID = 2048;
 constexpr int SK_LDS_MAX_GRID = 512;         // LDS path: docs/perf_notes.md "Sketches", grid sweep
 constexpr int SK_HIST = 66;                  // rho is in 0..65 - p <= 61; 66 as the contract says
-
-// Word i of a value (little endian); the bytes past its end are unspecified (the caller masks).
-struct LdsWords {
-    const uint32_t* w;     // the aligned LDS dword that holds the first byte
-    int sh;                // 8 * (byte position of the first byte in it)
-    __device__ __forceinline__ uint32_t operator()(int i) const {
-        const uint64_t pair = ((uint64_t)w[i + 1] << 32) | w[i];
-        return (uint32_t)(pair >> sh);
-    }
-};
-
-struct GlobalWords {
-    const uint8_t* q;
-    int len;
-    __device__ __forceinline__ uint32_t operator()(int i) const {
-        uint32_t k = 0;
-        for (int j = 0; j < 4; ++j)
-            if (4 * i + j < len) k |= (uint32_t)q[4 * i + j] << (8 * j);
-        return k;
-    }
-};
-
-template <typename Words>
-__device__ __forceinline__ uint32_t mm3(const Words& word, int len, uint32_t seed) {
-    uint32_t h = seed;
-    const int nw = len >> 2, r = len & 3;
-    for (int i = 0; i < nw; ++i) h = hm::mm_chain(h, hm::mm_premix(word(i)));
-    if (r) h ^= hm::mm_premix(word(nw) & ((1u << (8 * r)) - 1u));
-    return hm::mm_fmix(h, (uint32_t)len);
-}
 
 // the two halves of h64: one premix per word, two chains
 template <typename Words>
@@ -99,38 +67,6 @@ __device__ __forceinline__ uint64_t mm3_h64(const Words& word, int len) {
         hb ^= k;
     }
     return ((uint64_t)hm::mm_fmix(ha, (uint32_t)len) << 32) | hm::mm_fmix(hb, (uint32_t)len);
-}
-
-// The front end: calls op(s, words, len) once for every value s in 0..n-1, on the lane that owns
-// it.  s_stage holds SK_BYTES + 32 bytes: the window, its lead of up to 15 bytes and the dword
-// pair that LdsWords reads around the last byte.
-template <typename Op>
-__device__ __forceinline__ void sweep(const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
-                                      int64_t n, uint4* s_stage, Op& op) {
-    const int t = threadIdx.x;
-    for (int64_t base = (int64_t)blockIdx.x * SK_STRINGS; base < n; base += (int64_t)gridDim.x * SK_STRINGS) {
-        const int64_t last = n - base < SK_STRINGS ? n : base + SK_STRINGS;
-        const int64_t span0 = off[base], span = off[last] - span0;
-        const int staged = (int)(span < SK_BYTES ? span : SK_BYTES);
-        const uint8_t* g0 = buf + span0;
-        const int lead = (int)(reinterpret_cast<uintptr_t>(g0) & 15);
-        const int nvec = (lead + staged + 15) >> 4;
-        const uint4* gv = reinterpret_cast<const uint4*>(g0 - lead);
-        for (int v = t; v < nvec; v += SK_THREADS) s_stage[v] = gv[v];
-        __syncthreads();
-        const int64_t s = base + t;
-        if (s < last) {
-            const int64_t b = off[s] - span0, e = off[s + 1] - span0;
-            const int len = (int)(e - b);
-            if (e <= staged) {
-                const int a = lead + (int)b;
-                op(s, LdsWords{reinterpret_cast<const uint32_t*>(s_stage) + (a >> 2), 8 * (a & 3)}, len);
-            } else {
-                op(s, GlobalWords{g0 + b, len}, len);
-            }
-        }
-        __syncthreads();                        // the next step overwrites the window
-    }
 }
 
 // reg byte = max(reg byte, rho) on the 32-bit word that holds it (global memory or LDS)
@@ -187,21 +123,21 @@ struct HllOp {
 __global__ __launch_bounds__(SK_THREADS) void hll_direct_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ gid, int64_t n, int G, int p, uint32_t* __restrict__ reg) {
-    __shared__ uint4 s_stage[SK_BYTES / 16 + 2];
+    __shared__ uint4 s_stage[hm::stage_vecs(SK_BYTES)];
     HllOp op{gid, reg, G, p};
-    sweep(buf, off, n, s_stage, op);
+    hm::sweep<SK_STRINGS, SK_BYTES>(buf, off, n, s_stage, op);
 }
 
 __global__ __launch_bounds__(SK_THREADS) void hll_lds_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ gid, int64_t n, int G, int p, uint32_t* __restrict__ reg) {
-    __shared__ uint4 s_stage[SK_BYTES / 16 + 2];
+    __shared__ uint4 s_stage[hm::stage_vecs(SK_BYTES)];
     extern __shared__ uint32_t s_reg[];         // G * 2^p / 4 words
     const int nwords = (G << p) >> 2;
     for (int i = threadIdx.x; i < nwords; i += SK_THREADS) s_reg[i] = 0;
     __syncthreads();
     HllOp op{gid, s_reg, G, p};
-    sweep(buf, off, n, s_stage, op);            // ends with a barrier
+    hm::sweep<SK_STRINGS, SK_BYTES>(buf, off, n, s_stage, op);            // ends with a barrier
     // workgroups that finish together start their flushes at different words
     const int rot = (int)((blockIdx.x * 2654435761u) % (uint32_t)nwords);
     for (int j = threadIdx.x; j < nwords; j += SK_THREADS) {
@@ -254,7 +190,7 @@ struct BloomAddOp {
     __device__ __forceinline__ void operator()(int64_t s, const Words& word, int len) const {
         const int g = gid[s];
         if ((unsigned)g >= (unsigned)G) return;
-        const uint32_t h1 = mm3(word, len, 0u), h2 = mm3(word, len, h1);
+        const uint32_t h1 = hm::mm3(word, len, 0u), h2 = hm::mm3(word, len, h1);
         uint32_t i = h1 % m;
         const uint32_t d = h2 % m;
         uint32_t* row = bits + (int64_t)g * (m >> 5);
@@ -278,7 +214,7 @@ struct BloomTestOp {
     __device__ __forceinline__ void operator()(int64_t s, const Words& word, int len) const {
         const int f = fid[s];
         if ((unsigned)f >= (unsigned)F) { hit[s] = 0; return; }
-        const uint32_t h1 = mm3(word, len, 0u), h2 = mm3(word, len, h1);
+        const uint32_t h1 = hm::mm3(word, len, 0u), h2 = hm::mm3(word, len, h1);
         uint32_t i = h1 % m;
         const uint32_t d = h2 % m;
         const uint32_t* row = bits + (int64_t)f * (m >> 5);
@@ -295,18 +231,18 @@ struct BloomTestOp {
 __global__ __launch_bounds__(SK_THREADS) void bloom_add_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ gid, int64_t n, int G, uint32_t m, int k, uint32_t* __restrict__ bits) {
-    __shared__ uint4 s_stage[SK_BYTES / 16 + 2];
+    __shared__ uint4 s_stage[hm::stage_vecs(SK_BYTES)];
     BloomAddOp op{gid, bits, G, k, m};
-    sweep(buf, off, n, s_stage, op);
+    hm::sweep<SK_STRINGS, SK_BYTES>(buf, off, n, s_stage, op);
 }
 
 __global__ __launch_bounds__(SK_THREADS) void bloom_test_kernel(
         const uint8_t* __restrict__ buf, const int64_t* __restrict__ off,
         const int32_t* __restrict__ fid, int64_t n, const uint32_t* __restrict__ bits, int F, uint32_t m,
         int k, uint8_t* __restrict__ hit) {
-    __shared__ uint4 s_stage[SK_BYTES / 16 + 2];
+    __shared__ uint4 s_stage[hm::stage_vecs(SK_BYTES)];
     BloomTestOp op{fid, bits, hit, F, k, m};
-    sweep(buf, off, n, s_stage, op);
+    hm::sweep<SK_STRINGS, SK_BYTES>(buf, off, n, s_stage, op);
 }
 
 int sweep_grid(int64_t n, int cap) {

@@ -100,21 +100,17 @@ def _all_str_lists(rows) -> bool:
     return True
 
 
-def arrow_buffers(arr, wide: bool = True):
-    """(data uint8 ndarray, string offsets [n+1], row offsets int64 [B+1]) of a list<string>
-    array, rebased to start at 0 (slices honoured, zero-copy views where possible).  The string
-    offsets are int64, or (``wide=False``) the column's own int32 offsets when it has them —
-    a zero-copy view unless they need rebasing."""
+def string_buffers(vals, wide: bool = True):
+    """(data uint8 ndarray, offsets [n+1]) of a string or large-string array, rebased to start at
+    0 (slices honoured, zero-copy views where possible).  The offsets are int64, or
+    (``wide=False``) the array's own int32 offsets when it has them — a zero-copy view unless
+    they need rebasing."""
     import pyarrow as pa
 
-    lo = np.array(arr.offsets, dtype=np.int64)
-    vals = arr.values.slice(int(lo[0]), int(lo[-1] - lo[0]))
-    if lo[0]:
-        lo -= lo[0]
     bufs = vals.buffers()
     odt = np.int64 if pa.types.is_large_string(vals.type) else np.int32
     if bufs[1] is None:
-        so = np.zeros(1, np.int64)
+        so = np.zeros(len(vals) + 1, np.int64)
     else:
         so = np.frombuffer(bufs[1], dtype=odt)[vals.offset:vals.offset + len(vals) + 1]
         if wide or odt == np.int64:
@@ -124,7 +120,17 @@ def arrow_buffers(arr, wide: bool = True):
     data = data[int(so[0]):int(so[-1])] if len(so) else data[:0]
     if len(so) and so[0]:
         so = so - so[0]
-    return data, so, lo
+    return data, so
+
+
+def arrow_buffers(arr, wide: bool = True):
+    """(data uint8 ndarray, string offsets [n+1], row offsets int64 [B+1]) of a list<string>
+    array: ``string_buffers`` of its values plus the row offsets, all rebased to start at 0."""
+    lo = np.array(arr.offsets, dtype=np.int64)
+    vals = arr.values.slice(int(lo[0]), int(lo[-1] - lo[0]))
+    if lo[0]:
+        lo -= lo[0]
+    return (*string_buffers(vals, wide), lo)
 
 
 _POOL = None

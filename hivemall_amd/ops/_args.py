@@ -45,14 +45,3 @@ def all_finite(op: str, x: torch.Tensor, where) -> None:
     if bool(bad.any()):
         at = int(torch.nonzero(bad.reshape(-1))[0])
         raise ValueError(f"{op}: x[{where(at)}] is not finite ({float(x.reshape(-1)[at])})")
-
-
-def pad16(buf: torch.Tensor) -> torch.Tensor:
-    """The string kernels stage bytes in whole aligned 16-B chunks: a base that is 16-B aligned and
-    a length that is a multiple of 16 keep every such chunk inside the allocation."""
-    n = buf.numel()
-    if n and n % 16 == 0 and buf.data_ptr() % 16 == 0:
-        return buf
-    out = torch.zeros(max(16, (n + 15) // 16 * 16), dtype=torch.uint8, device=buf.device)
-    out[:n] = buf
-    return out

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from . import _args
+from . import _args, _packed
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -38,15 +38,6 @@ HASHES_PER_PASS = 256   # MH_HASHES
 MAX_GRID = 4096         # MH_MAX_GRID
 
 
-def _check_ptr(p: torch.Tensor, name: str) -> None:
-    if p.numel() < 1:
-        raise ValueError(f"minhash: {name} must hold at least one offset")
-    if int(p[0]) != 0:
-        raise ValueError(f"minhash: {name} must start at 0, got {int(p[0])}")
-    if p.numel() > 1 and bool((p[1:] < p[:-1]).any()):
-        raise ValueError(f"minhash: {name} must be non-decreasing")
-
-
 def minhash_signatures(buf: torch.Tensor, off: torch.Tensor, nlen: torch.Tensor, rowptr: torch.Tensor,
                        num_hashes: int, seed0: int = 0, *, check: bool = True) -> torch.Tensor:
     """int32 [n_rows, num_hashes]: the minhash signature of every row (uint32 bit patterns).
@@ -61,35 +52,25 @@ def minhash_signatures(buf: torch.Tensor, off: torch.Tensor, nlen: torch.Tensor,
     H = _args.int_in("minhash", num_hashes, "num_hashes", 1, H_MAX)
     seed0 = _args.int_in("minhash", seed0, "seed0", 0, 2**32 - 1)
     if check:
-        _check_ptr(off, "off")
-        _check_ptr(rowptr, "rowptr")
+        _packed.check_offsets("minhash", off, "off", buf)
+        _packed.check_offsets("minhash", rowptr, "rowptr")
     elif off.numel() < 1 or rowptr.numel() < 1:
         raise ValueError("minhash: off and rowptr must hold at least one offset")
     nnz = off.numel() - 1
     if nlen.numel() != nnz:
         raise ValueError(f"minhash: nlen must hold {nnz} lengths (off has {nnz + 1} offsets), "
                          f"got {nlen.numel()}")
-    if check and int(off[-1]) > buf.numel():
-        raise ValueError(f"minhash: off ends at {int(off[-1])}, buf holds {buf.numel()} bytes")
     if check and int(rowptr[-1]) != nnz:
         raise ValueError(f"minhash: rowptr must end at nnz = {nnz}, got {int(rowptr[-1])}")
     if check and nnz and bool(((nlen < 0) | (nlen.long() > off[1:] - off[:-1])).any()):
         raise ValueError("minhash: nlen[s] must be in 0..off[s + 1] - off[s]")
     n_rows = rowptr.numel() - 1
-    dev = buf.device
-    out = torch.empty((n_rows, H), dtype=torch.int32, device=dev)
+    out = torch.empty((n_rows, H), dtype=torch.int32, device=buf.device)
     if n_rows == 0:
         return out
-    buf, off, nlen, rowptr = (t.contiguous() for t in (buf, off, nlen, rowptr))
+    off, nlen, rowptr = (t.contiguous() for t in (off, nlen, rowptr))
     p = _native.ptr
-    rest = (p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out))
-    if buf.is_cuda:
-        buf = _args.pad16(buf)
-        _native.call_hip("hm_minhash_sig", dev, p(buf), *rest)
-    else:
-        if buf.numel() == 0:
-            buf = torch.zeros(1, dtype=torch.uint8)
-        _native.call_host("hm_minhash_sig", p(buf), *rest)
+    _packed.launch("hm_minhash_sig", buf, p(off), p(nlen), p(rowptr), n_rows, H, seed0, p(out))
     return out
 
 
@@ -127,16 +108,22 @@ def bbit_pack(sig: torch.Tensor, b: int) -> list:
 
 
 # ------------------------------------------------------------------ packing a column
+def _rows(col):
+    """A column that is not Arrow yet, as a list of lists for pyarrow, or None: pyarrow would read
+    a ``str`` row as a list of characters."""
+    import pandas as pd
+
+    if isinstance(col, (pd.Series, np.ndarray)):
+        col = col.tolist()
+    if isinstance(col, (list, tuple)) and all(r is None or isinstance(r, (list, tuple)) for r in col):
+        return col
+    return None
+
+
 def _arrow_list_of_strings(arr):
-    """One pyarrow list<string> array for ``arr`` or None when it is anything else."""
+    """``arr`` when it is a pyarrow list<string> array without NULL features, else None."""
     import pyarrow as pa
 
-    if isinstance(arr, pa.ChunkedArray):
-        if arr.num_chunks == 0:
-            return None
-        arr = arr.chunk(0) if arr.num_chunks == 1 else arr.combine_chunks()
-        if isinstance(arr, pa.ChunkedArray):
-            return None
     ty = arr.type
     if not (pa.types.is_list(ty) or pa.types.is_large_list(ty)):
         return None
@@ -166,31 +153,12 @@ def pack_feature_column(col):
     Arrow list<string>); a NULL row counts as an empty row.  None when the column holds anything
     else (ints, dicts, numeric arrays, NULL features) or a ``name:value`` whose value text is not
     a plain decimal: those keep the per-row functions and whatever they raise."""
-    import pandas as pd
     import pyarrow as pa
 
     from ..io.ingest import arrow_buffers
 
-    arr = col
-    if isinstance(arr, pd.Series):
-        arr = arr.array._pa_array if isinstance(arr.dtype, pd.ArrowDtype) else arr.tolist()
-    if not isinstance(arr, (pa.Array, pa.ChunkedArray)):
-        if isinstance(arr, np.ndarray):
-            arr = arr.tolist()
-        if not isinstance(arr, (list, tuple)):
-            return None
-        for r in arr:                                     # pyarrow would read a str as a list of chars
-            if r is not None and not isinstance(r, (list, tuple)):
-                return None
-        if len(arr) == 0:
-            arr = pa.array([], type=pa.list_(pa.string()))
-        else:
-            try:
-                arr = pa.array(arr)                       # inferred: mixed or non-string rows fail or differ
-            except (pa.ArrowInvalid, pa.ArrowTypeError, pa.ArrowNotImplementedError, UnicodeError,
-                    OverflowError):
-                return None
-    arr = _arrow_list_of_strings(arr)
+    arr = _packed.as_arrow(col, pa.list_(pa.string()), _rows)
+    arr = None if arr is None else _arrow_list_of_strings(arr)
     if arr is None:
         return None
     if not _null_rows_are_empty(arr):

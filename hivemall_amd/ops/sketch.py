@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from .. import _native
-from . import _args
+from . import _args, _packed
 
 _P = C.c_void_p
 _I64 = _native.c_i64
@@ -73,16 +73,9 @@ def _column(buf, off, ids, ids_name: str, n_ids: int, check: bool):
     if ids.numel() != n:
         raise ValueError(f"sketch: {ids_name} must hold {n} ids (off has {n + 1} offsets), got {ids.numel()}")
     if check:
-        if int(off[0]) != 0:
-            raise ValueError(f"sketch: off must start at 0, got {int(off[0])}")
-        if n:
-            d = off[1:] - off[:-1]
-            if bool((d < 0).any()):
-                raise ValueError("sketch: off must be non-decreasing")
-            if int(d.max()) >= 2**31:
-                raise ValueError("sketch: a value of 2^31 bytes or more")
-        if int(off[-1]) > buf.numel():
-            raise ValueError(f"sketch: off ends at {int(off[-1])}, buf holds {buf.numel()} bytes")
+        _packed.check_offsets("sketch", off, "off", buf)
+        if n and int((off[1:] - off[:-1]).max()) >= 2**31:
+            raise ValueError("sketch: a value of 2^31 bytes or more")
         if n and (int(ids.min()) < 0 or int(ids.max()) >= n_ids):
             raise ValueError(f"sketch: {ids_name} must be in 0..{n_ids - 1}")
     return n
@@ -98,10 +91,6 @@ def _state(t, name: str, shape: tuple, device) -> torch.Tensor:
     if not t.is_contiguous() or t.data_ptr() % 16:
         raise ValueError(f"sketch: {name} must be contiguous and 16-byte aligned")
     return t
-
-
-def _host_buf(buf: torch.Tensor) -> torch.Tensor:
-    return buf if buf.numel() else torch.zeros(1, dtype=torch.uint8)
 
 
 def hll_registers(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: int, p: int,
@@ -125,16 +114,11 @@ def hll_registers(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: in
         return reg
     off, gid = off.contiguous(), gid.contiguous()
     ptr = _native.ptr
-    if buf.is_cuda:
-        buf = _args.pad16(buf.contiguous())
-        if _lds_grid:                                     # benchmarks/sketch_bench.py --sweep
-            _native.call_hip("hm_hll_update_grid", dev, ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg),
-                             int(_lds_grid))
-        else:
-            _native.call_hip("hm_hll_update", dev, ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg))
+    rest = (ptr(off), ptr(gid), n, G, p, ptr(reg))
+    if _lds_grid and buf.is_cuda:                         # benchmarks/sketch_bench.py --sweep
+        _packed.launch("hm_hll_update_grid", buf, *rest, int(_lds_grid))
     else:
-        buf = _host_buf(buf.contiguous())
-        _native.call_host("hm_hll_update", ptr(buf), ptr(off), ptr(gid), n, G, p, ptr(reg))
+        _packed.launch("hm_hll_update", buf, *rest)
     return reg
 
 
@@ -216,12 +200,7 @@ def bloom_bits(buf: torch.Tensor, off: torch.Tensor, gid: torch.Tensor, G: int, 
         return bits
     off, gid = off.contiguous(), gid.contiguous()
     ptr = _native.ptr
-    if buf.is_cuda:
-        buf = _args.pad16(buf.contiguous())
-        _native.call_hip("hm_bloom_add", dev, ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits))
-    else:
-        buf = _host_buf(buf.contiguous())
-        _native.call_host("hm_bloom_add", ptr(buf), ptr(off), ptr(gid), n, G, m, k, ptr(bits))
+    _packed.launch("hm_bloom_add", buf, ptr(off), ptr(gid), n, G, m, k, ptr(bits))
     return bits
 
 
@@ -246,16 +225,30 @@ def bloom_test(bits: torch.Tensor, fid: torch.Tensor, buf: torch.Tensor, off: to
         return hit
     off, fid = off.contiguous(), fid.contiguous()
     ptr = _native.ptr
-    if buf.is_cuda:
-        buf = _args.pad16(buf.contiguous())
-        _native.call_hip("hm_bloom_test", dev, ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit))
-    else:
-        buf = _host_buf(buf.contiguous())
-        _native.call_host("hm_bloom_test", ptr(buf), ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit))
+    _packed.launch("hm_bloom_test", buf, ptr(off), ptr(fid), n, ptr(bits), F, m, k, ptr(hit))
     return hit
 
 
 # ------------------------------------------------------------------ packing a column
+def _values(col):
+    """A column that is not Arrow yet, as pyarrow takes it, or None: object columns as a list,
+    integer ones as an Arrow array."""
+    import pandas as pd
+    import pyarrow as pa
+
+    if isinstance(col, pd.Series):
+        if col.dtype == object:
+            return col.tolist()
+        if pd.api.types.is_integer_dtype(col.dtype) and not pd.api.types.is_bool_dtype(col.dtype):
+            return pa.Array.from_pandas(col)
+        return None
+    if isinstance(col, np.ndarray):
+        if col.ndim != 1:
+            return None
+        return pa.array(col) if col.dtype.kind in "iu" else col.tolist() if col.dtype == object else None
+    return col
+
+
 def pack_value_column(col):
     """``(buf uint8, off int64 [n + 1], keep int64 [n])`` CPU tensors for a column of values: the
     UTF-8 text of every non-NULL value back to back, and the positions of those values in the
@@ -263,43 +256,13 @@ def pack_value_column(col):
     and an integer column, as the decimal text ``str(int)`` gives.  None for anything else
     (floats, bools, bytes, nested or mixed values): those keep the per-value Python loop and its
     ``str(v)``."""
-    import pandas as pd
     import pyarrow as pa
 
-    arr = col
-    if isinstance(arr, pd.Series):
-        if isinstance(arr.dtype, pd.ArrowDtype):
-            arr = arr.array._pa_array
-        elif arr.dtype == object:
-            arr = arr.tolist()
-        elif pd.api.types.is_integer_dtype(arr.dtype) and not pd.api.types.is_bool_dtype(arr.dtype):
-            try:
-                arr = pa.Array.from_pandas(arr)
-            except (pa.ArrowInvalid, pa.ArrowTypeError, pa.ArrowNotImplementedError):
-                return None
-        else:
-            return None
-    if isinstance(arr, np.ndarray):
-        if arr.ndim != 1:
-            return None
-        arr = pa.array(arr) if arr.dtype.kind in "iu" else arr.tolist() if arr.dtype == object else None
-        if arr is None:
-            return None
-    if not isinstance(arr, (pa.Array, pa.ChunkedArray)):
-        if not isinstance(arr, (list, tuple)):
-            return None
-        if len(arr) == 0:
-            arr = pa.array([], type=pa.string())
-        else:
-            try:
-                arr = pa.array(arr)                       # inferred: mixed columns fail or differ
-            except (pa.ArrowInvalid, pa.ArrowTypeError, pa.ArrowNotImplementedError, UnicodeError,
-                    OverflowError):
-                return None
-    if isinstance(arr, pa.ChunkedArray):
-        arr = arr.combine_chunks() if arr.num_chunks != 1 else arr.chunk(0)
-        if isinstance(arr, pa.ChunkedArray):
-            return None
+    from ..io.ingest import string_buffers
+
+    arr = _packed.as_arrow(col, pa.string(), _values)
+    if arr is None:
+        return None
     ty = arr.type
     if pa.types.is_null(ty):
         arr = pa.array([None] * len(arr), type=pa.string())
@@ -311,19 +274,8 @@ def pack_value_column(col):
     if arr.null_count:
         keep = np.flatnonzero(np.asarray(arr.is_valid())).astype(np.int64)
         arr = arr.drop_null()
-    if not pa.types.is_large_string(arr.type):
-        arr = arr.cast(pa.large_string())
-    n = len(arr)
-    bufs = arr.buffers()
-    if n == 0 or bufs[1] is None:
-        so = np.zeros(n + 1, np.int64)
-        data = np.zeros(0, np.uint8)
-    else:
-        so = np.frombuffer(bufs[1], dtype=np.int64)[arr.offset:arr.offset + n + 1]
-        raw = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
-        data = raw[int(so[0]):int(so[-1])]
-        so = so - so[0]
-    if n and int(np.max(so[1:] - so[:-1])) >= 2**31:
+    data, so = string_buffers(arr)
+    if len(arr) and int(np.max(so[1:] - so[:-1])) >= 2**31:
         return None
     return (torch.from_numpy(np.array(data, dtype=np.uint8)), torch.from_numpy(np.array(so, dtype=np.int64)),
             torch.from_numpy(keep))

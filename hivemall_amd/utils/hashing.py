@@ -6,7 +6,7 @@ MurmurHash3_x86_32 over the UTF-8 bytes, seed 0x9747b28c, ``h % num_features`` w
 remainder semantics, negatives shifted into range, result starting from 1.
 
 The batch paths run in the native host library (``csrc/host/hashing.cpp``) and, for device
-resident string buffers, in the gfx950 kernel ``csrc/kernels/mhash.hip``.
+resident string buffers, in the gfx950 kernel ``csrc/kernels/hashing.hip``.
 """
 from __future__ import annotations
 
@@ -126,30 +126,8 @@ def mhash_device(words: Iterable[str], num_features: int = DEFAULT_NUM_FEATURES,
     returns the raw signed 32-bit hashes.  Bit-exact with :func:`mhash_batch`."""
     import torch
 
-    from .. import _native
+    from ..ops._packed import mhash_packed
 
-    words = list(words)
-    buf, off = pack_strings(words)
-    dev = torch.device(device)
-    out = torch.empty(len(words), dtype=torch.int32, device=dev)
-    if not words:
-        return out
-    b = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8).copy() if buf else np.zeros(16, np.uint8))
-    # pad so the kernel's 16-B staging loads never run past the allocation
-    b = torch.cat([b, torch.zeros(16, dtype=torch.uint8)]).to(dev)
-    o = torch.from_numpy(off.astype(np.int64)).to(dev)
-    rc = _native.hip().hm_mhash(_native.ptr(b), _native.ptr(o), len(words), seed, int(num_features),
-                                _native.ptr(out), _native.stream_of(dev))
-    _native.check(rc, "hm_mhash")
-    return out
-
-
-def _register():
-    import ctypes as C
-
-    from .. import _native
-    _native.register_hip("hm_mhash", [_native.c_p, _native.c_p, _native.c_i64, C.c_uint32, C.c_int32,
-                                      _native.c_p, _native.c_p])
-
-
-_register()
+    buf, off = pack_strings(list(words))
+    b = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8).copy())
+    return mhash_packed(b.to(device), torch.from_numpy(off).to(device), int(num_features), seed)

@@ -78,6 +78,77 @@ def test_shared_header_compiled_for_the_host(tmp_path):
     assert f"checked {len(VECTORS)} bad 0" in r.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_string_front_end_compiled_for_the_host(tmp_path):
+    """The word loaders and mm3 of csrc/kernels/strspan.h (tests/native/strspan_kat.cpp): every
+    start position 0..15 x length 0..40 x 4 seeds against murmur3_bytes, then the vectors."""
+    exe = tmp_path / "strspan_kat"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(HERE, "native", "strspan_kat.cpp"),
+                           "-o", str(exe)])
+    args = []
+    for data, seed, want in VECTORS:
+        args += [data.hex() or "-", f"{seed:x}", f"{want:x}"]
+    r = subprocess.run([str(exe)] + args, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert f"grid {16 * 41 * 4} vectors {len(VECTORS)} bad 0" in r.stdout
+
+
+# ------------------------------------------------------------------ hm_mhash over its own window
+MHASH_STRINGS, MHASH_BYTES = 256, 16384          # HASH_STRINGS, HASH_LDS of csrc/kernels/hashing.hip
+
+
+def _window_cases() -> dict:
+    S, W = MHASH_STRINGS, MHASH_BYTES
+    each = W // S
+    cases = {
+        "edge_lengths": [b"q" * n for n in (*range(10), 31, 32, 33)],
+        "utf8": [s.encode() for s in ("日本語", "特徴量", "😀", "😀😀x", "é", "aé😀日", "\u0000", "a\u0000b")],
+        "beyond_window": [b"", b"s0", b"L" * (W + 100), b"s1", b"", b"N" * (W + 1), b"", b"s2", b""],
+        "five_windows": [b"", b"M" * (5 * W + 3), b""],
+    }
+    # a first full step before the run: 256 two-byte strings (512 bytes), and 256 strings of 2-4
+    # bytes (914 bytes) so that the second step's span does not start at a multiple of 16
+    two = [b"%02x" % i for i in range(S)]
+    odd = [b"p%d" % i for i in range(S)]
+    assert sum(map(len, two)) % 16 == 0 and sum(map(len, odd)) % 16 == 2
+    for d in (-1, 0, 1):
+        cases[f"count{d:+d}"] = [b"c%d" % i for i in range(S + d)]
+        run = [(b"%04d" % i).ljust(each, b"r") for i in range(S - 1)] + [(b"%04d" % S).ljust(each + d, b"e")]
+        assert len(run) == S and sum(map(len, run)) == W + d
+        cases[f"bytes{d:+d}"] = run
+        cases[f"bytes{d:+d}_after_two_byte_step"] = two + run + [b"after", b""]
+        cases[f"bytes{d:+d}_after_odd_step"] = odd + run + [b"after", b""]
+    return cases
+
+
+WINDOW = _window_cases()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(WINDOW))
+def test_device_kernel_window(case):
+    """hm_mhash at the edges of its tiling: raw hashes against murmur3_batch, mhash against
+    mhash_batch; the buffer as uploaded and as a misaligned view that launch() has to re-pad."""
+    import torch
+
+    from hivemall_amd.ops._packed import mhash_packed
+    from hivemall_amd.utils.hashing import mhash_batch, pack_strings
+
+    words = WINDOW[case]
+    raw, off = pack_strings(words)
+    buf = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).cuda()
+    big = torch.full((buf.numel() + 64,), 0xFF, dtype=torch.uint8, device="cuda")
+    view = big[3:3 + buf.numel()]
+    view.copy_(buf)
+    assert view.data_ptr() % 16 == 3
+    off = torch.from_numpy(off).cuda()
+    for seed in SEEDS:
+        for nf, want in ((0, murmur3_batch(words, seed)), (1 << 24, mhash_batch(words, 1 << 24, seed))):
+            for b in (buf, view):
+                got = mhash_packed(b, off, nf, seed).cpu().numpy()
+                assert np.array_equal(got, want), f"seed {seed:#x} num_features {nf}"
+
+
 @pytest.mark.gpu
 def test_device_kernel():
     """hm_mhash with num_features = 0 returns the raw hash: one launch per distinct seed."""
