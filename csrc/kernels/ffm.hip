@@ -218,7 +218,8 @@ __device__ __forceinline__ void hacc_publish(float* __restrict__ hacc, int nhot,
 // rows).  Measured (profiles/r6/linhot/): 8,192 blocks 76.0 M rows/s, 4,096 82.4 M (+0.90e-3),
 // 2,048 84.2-84.8 M at +0.96e-3 .. +1.01e-3; 1,024 (256 rows per block) diverges (+0.06 .. +0.11): every block walks
 // its own copy of a hot feature's weight toward the target for 256 rows and the sum of those walks
-// overshoots.
+// overshoots.  The 512-thread blocks of round 10 leave it alone: LDS (77.9 KB a block, whatever the
+// thread count) sets the blocks per CU, so 512 stay resident and 2,048 stays four full rounds.
 constexpr int HACC_GRID = 2048;
 // The bf16 kernel holds 3 blocks per CU (768 resident), so 2,048 blocks leave its last round 2/3
 // full: 2,304 (3 full rounds) 128.1-128.9 M bf16 rows/s at +1.58e-3 .. +1.67e-3 vs 125.8-125.9 M at
@@ -1121,7 +1122,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     float* __restrict__ bias, float* __restrict__ pred_out, float* __restrict__ loss_out)
 {
     constexpr bool SPEC = (CFG & SG32_TRAIN) != 0;
-    static_assert(!SPEC || (ATOM == 0 && KV == 1 && KEEP >= 2 && sizeof(OT) == 4 && TPB == 256),
+    // TPB: whole waves, at least the 4 the role waves need; NS: okm packs 8 bits per predicate, and
+    // the image index t < NS TPB shares ab[] with a and b (16 bits)
+    static_assert(!SPEC || (ATOM == 0 && KV == 1 && KEEP >= 2 && sizeof(OT) == 4 && TPB % 64 == 0 &&
+                            TPB >= 256 && NS <= 8 && NS * TPB < (1 << 15)),
                   "SG32_TRAIN: the default fp32 k <= 4 training launch only");
     // per-launch constants: fixed by the configuration, else the launch's (macros, so that CFG = 0
     // tests P.x exactly where it did)
@@ -1301,6 +1305,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     // side-table DMA, per lane < F of W_LIN and row, none of them predicated on the feature);
     // 2 NS slot DMAs per wave and row (KV == 1); with LT one s_nh DMA in phase B, older than the
     // slot DMAs; and 3 meta DMAs (idx, fld, val) on W_DMA only, which waits with vmcnt(0).
+    // The wait before D follows NS, not TPB: vmcnt(2 NS), i.e. vmcnt(6) for the 512-thread default
+    // at 33 .. 39 fields (NS = 3) and vmcnt(12) for variant 12's 256 threads there (NS = 6); at most
+    // vmcnt(16), the counter holds 63.
     const int nlin = (c_linear && c_ldefer) ? ((c_lpack || !c_train) ? 1 + (LT != 0) : 3) : 0;
     auto dma_lin = [&](int bf) {
         if (c_linear && wave == W_LIN && lane < F) {
@@ -2139,6 +2146,36 @@ int dispatch_sg12(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t st
     });
 }
 
+// Threads per block of the specialised training launch (round 10).  A row's F F slots are spread
+// over TPB threads, NS = ceil(F F / TPB) slots each; the block's LDS does not depend on TPB (the
+// landing zones and the image hold NS TPB >= F F entries either way), so the CU still holds two
+// blocks = two rows in flight, each walked by TPB / 64 waves: 512 threads = 3 slots a thread at 39
+// fields, 4 waves per SIMD to cover each other's stalls instead of 2 (126 VGPRs, no scratch).
+// Measured, one box, parent / 384 / 512 threads: 91.3 / 78.1 / 92.9 M rows/s, and 96.2 / 98.8 M on a
+// second box (docs/perf_notes.md round 10).  The phases between two barriers are bound by what
+// each SIMD issues for the block: one wave of 6 slots at 256 threads, two waves of 3 at 512, but
+// two waves of 4 on SIMDs 0 and 1 at 384 (waves w and w + 4 share a SIMD), which is why 384 loses.
+// At 512 every SIMD holds two of the block's waves whatever the role waves' numbers, so W_META,
+// W_LIN and W_DMA stay 1, 2, 3; at 384, W_LIN on wave 4 (SIMD 0, shared with wave 0) instead of
+// wave 2 (alone on SIMD 2): 73.2 vs 78.1 M.
+constexpr int SG32_TRAIN_TPB = 512;
+
+// The training launch the specialised configuration covers (dispatch_sg32's `spec`), on TPB-thread
+// blocks: CFG = SG32_TRAIN or 0 (variant 11), LT = the side table is on.  F <= 45: at most 2,025
+// slots, so the ladders end at 8 x 256 and 4 x 512 (the same 2,048 entries of LDS).
+template <int TPB, int CFG>
+void launch_sg32_train(const FFMParams& Q, const FFMArgs& a, int blocks, hipStream_t stream) {
+    const int need = (Q.F * Q.F + TPB - 1) / TPB;
+    auto go = [&](auto ns) {
+        constexpr int NS = decltype(ns)::value;
+        if (Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, TPB, 0, 1, 2, 1, CFG>, blocks, TPB, 0, stream, Q, a);
+        else launch(ffm_pipe_sg32_kernel<NS, uint32_t, TPB, 0, 1, 2, 0, CFG>, blocks, TPB, 0, stream, Q, a);
+    };
+    static_assert(TPB == 256 || TPB == 512, "a slot-count ladder for this TPB");
+    if constexpr (TPB == 512) with_ns<2, 3, 4>(need, go);   // F <= 32, <= 39, <= 45
+    else with_ns<2, 4, 6, 8>(need, go);
+}
+
 // Per-slot-G fp32 pipelined dispatch (Kp == 4 or 8, F <= 45, block layout): the LDS-DMA
 // ffm_pipe_sg32_kernel; -1 otherwise (bf16 V in this layout: the generic kernel; the bf16 default
 // is the 12-B slot layout of dispatch_sg12).
@@ -2171,16 +2208,23 @@ int dispatch_sg32(const FFMParams& P, const FFMArgs& a, int grid, int variant, h
         });
     // The default kernel choice (variant 0) of a training launch of the default learner takes the
     // instantiation specialised for it (SG32_TRAIN above); anything else — predict, -w0, separate
-    // linear arrays, implicit fields or values, wide tables, the all-atomic ramp — the generic one.
-    // Variant 11 = the same launch (LT, KEEP, grid) on the generic instantiation.
-    const bool spec = variant == 0 && !wide && P.train && P.use_linear && P.lpack && P.lin_defer &&
-                      !P.use_bias && a.fld && a.val && (size_t)P.fstride * 16 == (size_t)P.gstride * 4;
+    // linear arrays, implicit fields or values, wide tables, the all-atomic ramp — the generic one
+    // on 256-thread blocks.  Variant 11 = the same launch (TPB, NS, LT, KEEP, grid) on the generic
+    // instantiation.
+    // Variant 12 = the specialised instantiation on the 256-thread blocks it ran on before round 10.
+    const bool spec = (variant == 0 || variant == 11 || variant == 12) && !wide && P.train && P.use_linear &&
+                      P.lpack && P.lin_defer && !P.use_bias && a.fld && a.val &&
+                      (size_t)P.fstride * 16 == (size_t)P.gstride * 4;
+    if (spec)
+        return with_side_table(Q, a.w, stream, [&] {
+            if (variant == 12) launch_sg32_train<256, SG32_TRAIN>(Q, a, blocks, stream);
+            else if (variant == 11) launch_sg32_train<SG32_TRAIN_TPB, 0>(Q, a, blocks, stream);
+            else launch_sg32_train<SG32_TRAIN_TPB, SG32_TRAIN>(Q, a, blocks, stream);
+        });
     return with_side_table(Q, a.w, stream, [&] {
         with_ns<2, 4, 6, 8>(need, [&](auto ns) {
             constexpr int NS = decltype(ns)::value;
             if (wide) launch(ffm_pipe_sg32_kernel<NS, uint64_t>, blocks, 256, 0, stream, Q, a);
-            else if (spec && Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 1, SG32_TRAIN>, blocks, 256, 0, stream, Q, a);
-            else if (spec) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 0, SG32_TRAIN>, blocks, 256, 0, stream, Q, a);
             else if (variant == 6) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 1>, blocks, 256, 0, stream, Q, a);
             else if (Q.hacc_on) launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2, 1>, blocks, 256, 0, stream, Q, a);
             else launch(ffm_pipe_sg32_kernel<NS, uint32_t, 256, 0, 1, 2>, blocks, 256, 0, stream, Q, a);
@@ -2281,7 +2325,10 @@ int launch_deferred(FFMParams P, const FFMArgs& a, int slot_g, int grid_req, hip
 // added by float atomics (no lost update; the learner's early-training ramp, models/ffm.py
 // RAMP_*), 11 = the default sg32 kernel choice (same LT, KEEP and grid) forced onto the generic
 // instantiation, CFG = 0, where the default takes the one specialised for a training launch
-// (SG32_TRAIN; round 7, k <= 4 only).  Any other value is an error.  Measured and removed:
+// (SG32_TRAIN; round 7, k <= 4 only), 12 = that specialised instantiation on 256-thread blocks,
+// 6 slots a thread at 39 fields, where the default runs SG32_TRAIN_TPB = 512 threads, 3 slots a
+// thread (round 10; a launch the specialisation does not cover runs as under 0).  Any other value
+// is an error.  Measured and removed:
 //   2, ffm_lean_kernel on bf16 state: 88 vs 101 M rows/s (profiles/ffm_r2/ab_pipe_v1.log ...);
 //   3, ffm_pipe_kernel on fp32 state: 52.5 vs 51.2 M rows/s, held-out +0.019 vs +0.010 at 500 K rows
 //      (profiles/ffm_r2/fp32_pipe_ab.log);
@@ -2293,7 +2340,8 @@ int launch_deferred(FFMParams P, const FFMArgs& a, int slot_g, int grid_req, hip
 //   lin_atomic 1 - 3, float atomics on the linear records (all / flagged / unflagged features):
 //      8.7 / 8.7 / 82.6 M rows/s, the last at an unchanged gap (profiles/r6/linhot/).
 // Also measured and removed: 512-thread sg32
-// blocks (75.7-76.1 vs 75.6 M rows/s, profiles/r4/ffm_512_thread_ab.log); a paired-slot sg32
+// blocks (75.7-76.1 vs 75.6 M rows/s on round 4's kernel, profiles/r4/ffm_512_thread_ab.log; round
+// 10 measured them again on the specialised kernel and kept them, SG32_TRAIN_TPB); a paired-slot sg32
 // kernel holding each (a, b) / (b, a) slot pair in one thread's registers instead of a transposed
 // LDS image (4 rows in flight per CU instead of 2): 58.1-58.4 vs 74.9-75.5 M rows/s — the (b, a)
 // halves of a wave's pairs are V[i_b][f_a] for 64 different features, 16-B loads from 64
@@ -2331,7 +2379,7 @@ HM_API int hm_ffm_step(const int32_t* ip, const float* hp, const int32_t* idx, c
     P.seed = (uint32_t)ip[13];
     const int packed = ip[14];
     const int variant = ip[15];
-    if (variant != 0 && variant != 1 && variant != 6 && variant != 11) return (int)hipErrorInvalidValue;
+    if (variant != 0 && variant != 1 && variant != 6 && variant != 11 && variant != 12) return (int)hipErrorInvalidValue;
     if (ip[26] != 0 && ip[26] != 4) return (int)hipErrorInvalidValue;
     P.sstride = packed ? 2 * P.Kp : P.Kp;
     P.fstride = ip[16] > 0 ? ip[16] : P.num_fields;

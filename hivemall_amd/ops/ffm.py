@@ -42,8 +42,9 @@ class FFMHyper:
 
 _CALLS = 0  # per-launch counter mixed into the stochastic-rounding seed
 # kernel variant: 0 = auto, 1 = the generic ffm_row_kernel, 6 = all-atomic slot updates (the learner's
-# ramp), 11 = the default launch on the generic sg32 instantiation (hm_ffm_step lists the retired ones)
-VARIANTS = (0, 1, 6, 11)
+# ramp), 11 = the default launch on the generic sg32 instantiation, 12 = the specialised sg32 training
+# launch on 256-thread blocks instead of 512 (hm_ffm_step lists the retired ones)
+VARIANTS = (0, 1, 6, 11, 12)
 _VARIANT = int(os.environ.get("HM_FFM_VARIANT", "0"))
 
 
