@@ -16,11 +16,14 @@ end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_en
 body = lines[start:end + 1]
 labels = {m.group(1): i for i, l in enumerate(body) if (m := re.match(r"^(\.LBB\d+_\d+):", l))}
 lo, hi = 1 << 30, 0
+# the prologue's first barrier is outside the row loop: a backward branch over it is a cold block
+# laid out behind the function that jumps back into the prologue (the side table's gated publish)
+first_bar = next((i for i, l in enumerate(body) if "s_barrier" in l), 1 << 30)
 for i, l in enumerate(body):
     m = re.search(r"s_c?branch\S*\s+(\.LBB\d+_\d+)", l)
     if m and labels.get(m.group(1), 1 << 30) < i:
         t = labels[m.group(1)]
-        if any("s_barrier" in x for x in body[t:i]):
+        if t > first_bar and any("s_barrier" in x for x in body[t:i]):
             lo, hi = min(lo, t), max(hi, i)
 loop = body[lo:hi + 1]
 if len(sys.argv) > 3:

@@ -87,7 +87,7 @@ struct FFMParams {
     int lin_atomic;
     const int32_t* hidx;           // lin_atomic 4: hot index of each feature (-1: cold), [num_features]
     const int32_t* hot_id;         // lin_atomic 4: feature of each hot index, [nhot]
-    float* hacc;                   // lin_atomic 4: ACC {z, n} [nhot], then READ {z, n, 0, 0} [nhot] (HD_SIZE below)
+    float* hacc;                   // lin_atomic 4: ACC {z, n} [nhot], READ {z, n, 0, 0} [nhot], the gate's control block (HD_SIZE below)
     int nhot;                      // <= HD_SIZE
     int hacc_on;                   // set by the dispatch for a launch that uses the side table
     // Global-bias FTRL state sharded over bias_s 128-B lines during a training launch (sg32 /
@@ -171,14 +171,20 @@ __device__ __forceinline__ void bias_update_sh(const FFMParams& P, float g, floa
 //          the only place a flushed step lives (ffm_hacc_kernel folds ACC back into the records).
 //   READ = P.hacc + hacc_read_off(nhot), nhot entries {z, n, 0, 0} of 16 B: what the rows DMA.
 //          Nothing ever adds to it atomically.
-// Every block copies ACC to READ before its first row (hacc_publish).  Why that is enough:
+// A block copies ACC to READ before its first row (hacc_publish) when its XCD has not yet seen
+// T (the control block's EVERY) of the launch's flushes (the gate: hacc_ctl_off below; round 11).  Until
+// round 11 every block did; the blocks of the first round copied ACC onto an equal READ (dir 0 had
+// just written both, nothing had been flushed), and every later one could add only the one or two
+// flushes that had landed since the XCD's previous block start.  With the gate READ lags ACC by
+// fewer than T flushes chip-wide plus the flushes in flight, instead of by one block start on the
+// XCD; T = 1 skips only the copies that cannot change READ.  Why a publish is enough:
 //  - plain stores keep the line in the storing XCD's L2, so a block's publish is visible to every
 //    row on its XCD at once, and the rows' READ DMAs are L2 hits that no atomic ever drops (a float
 //    atomic executes at the memory side and drops its line from the XCD's L2: with one table, each
 //    flush sent the rows of its XCD back to memory for the lines it had touched);
 //  - the L2s are not coherent with each other inside a launch, so each XCD keeps its own copy of
-//    READ, refreshed by its own blocks' starts: 64 resident fp32 blocks per XCD at about 0.73 ms each
-//    at the bench shape, one refresh per ~11 us;
+//    READ, refreshed by its own publishing blocks (64 resident fp32 blocks per XCD at about 0.73 ms
+//    each at the bench shape: one block start per ~11 us, each a publish before the gate);
 //  - a block starts right after a block on the same CU ended, whose flush dropped the ACC lines it
 //    touched from this XCD's L2 (16 entries per line: nearly every block touches every line), so
 //    the publish reads ACC from the memory side (its loads bypass the CU's L1);
@@ -198,8 +204,45 @@ constexpr int HACC_READ_STRIDE = 4;
 // READ's offset in P.hacc, in floats: behind ACC's 2 nhot, on a 128-B line (hivemall_amd/ops/ffm.py
 // _lin_hot_tables allocates by the same rule)
 __host__ __device__ __forceinline__ int hacc_read_off(int nhot) { return (2 * nhot + 31) & ~31; }
+// The publish gate's control block (round 11), in floats from P.hacc: behind READ's 4 nhot, on a
+// 128-B line of its own, ten lines of one uint32 each (hivemall_amd/ops/ffm.py _hacc_ctl_off is the
+// same rule):
+//   line 0      FLUSHED: blocks of this launch that have issued their flush (one no-return agent
+//               add per block, un-waited like the flush; ffm_hacc_kernel dir 0 zeroes it)
+//   lines 1..8  SEEN[x]: FLUSHED as XCD x's last publishing block read it (plain store: the line
+//               stays in that XCD's L2, like READ; zeroed by dir 0)
+//   line 9      EVERY: the threshold T, written by the host when the table is created; no atomic
+//               ever touches its line.  0 = every block publishes.
+__host__ __device__ __forceinline__ int hacc_ctl_off(int nhot) { return (hacc_read_off(nhot) + 4 * nhot + 31) & ~31; }
+constexpr int HACC_CTL_LINE = 32;       // floats per 128-B line
+constexpr int HACC_CTL_SEEN = 1, HACC_CTL_EVERY = 9, HACC_CTL_LINES = 10;
 
-// ACC -> READ, by every thread of a block before its first row: coalesced loads that bypass the
+// The gate's three loads, by one lane of a block before its first row (issued with the first row's
+// metadata DMA, so the prologue's vmcnt(0) covers them): does this block copy ACC to READ?  It does
+// iff at least EVERY flushes have been counted since its XCD's last publish.  x = the XCD this
+// wave runs on (HW_REG_XCC_ID, bits 3:0).  The marks are advisory: a stale FLUSHED or SEEN costs a
+// publish too many or too few, never a step (sums live only in ACC).
+struct HaccGate { uint32_t flushed, seen, every; int x; };
+__device__ __forceinline__ HaccGate hacc_gate_load(float* __restrict__ hacc, int nhot) {
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(hacc + hacc_ctl_off(nhot));
+    HaccGate g;
+    g.x = (int)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u);   // hwreg(HW_REG_XCC_ID, 0, 4)
+    g.flushed = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    g.seen = __hip_atomic_load(ctl + HACC_CTL_LINE * (HACC_CTL_SEEN + g.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    g.every = __hip_atomic_load(ctl + HACC_CTL_LINE * HACC_CTL_EVERY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return g;
+}
+__device__ __forceinline__ bool hacc_gate_open(const HaccGate& g) { return g.flushed - g.seen >= g.every; }
+// the publishing block's mark: plain store
+__device__ __forceinline__ void hacc_gate_mark(float* __restrict__ hacc, int nhot, const HaccGate& g) {
+    reinterpret_cast<uint32_t*>(hacc + hacc_ctl_off(nhot))[HACC_CTL_LINE * (HACC_CTL_SEEN + g.x)] = g.flushed;
+}
+// a block's count of its flush: one lane, after the flush atomics were issued, not waited for
+__device__ __forceinline__ void hacc_count_flush(float* __restrict__ hacc, int nhot) {
+    __hip_atomic_fetch_add(reinterpret_cast<uint32_t*>(hacc + hacc_ctl_off(nhot)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ACC -> READ, by every thread of a publishing block before its first row: coalesced loads that bypass the
 // CU's L1 (an earlier block's publish may have left the lines there), plain 16-B stores.
 template <int TPB>
 __device__ __forceinline__ void hacc_publish(float* __restrict__ hacc, int nhot, int tid) {
@@ -1153,6 +1196,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     __shared__ float2 s_hd[LT ? HD_SIZE : 1];
     __shared__ __attribute__((aligned(16))) float4 s_hacc[LT ? 2 : 1][48];
     __shared__ __attribute__((aligned(16))) int s_nh[LT ? 2 : 1][48];   // DMA of the rows' hot indices
+    __shared__ int s_pub;                                               // LT: this block publishes (the gate)
     const int F = P.F;
     const int FF = F * F;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1330,12 +1374,30 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
     if (row >= P.B) return;
     if (tid == 0) { s_bcur[0] = 0.f; s_bcur[1] = 0.f; }
     dma_meta(0, row);
+    // LT: the publish gate (hacc_gate_load above).  Thread 0 loads the counters next to the metadata
+    // DMA and hands the block-uniform answer over in s_pub behind the barrier; only a publishing
+    // block copies ACC -> READ (HD_SIZE above) and waits for its stores before the second barrier,
+    // which is the one the first row's READ DMA (dma_lin below) is behind either way.
+    HaccGate gate = {0u, 0u, 0u, 0};
     if constexpr (LT != 0) {
-        if (c_hacc) hacc_publish<TPB>(P.hacc, P.nhot, tid);   // ACC -> READ (HD_SIZE above)
+        if (c_hacc && tid == 0) gate = hacc_gate_load(P.hacc, P.nhot);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
+    if constexpr (LT != 0) {
+        if (c_hacc && tid == 0) {
+            const bool open = hacc_gate_open(gate);
+            s_pub = open;
+            if (open) hacc_gate_mark(P.hacc, P.nhot, gate);
+        }
+    }
     bar_raw();
     publish_meta(0);
+    if constexpr (LT != 0) {
+        if (c_hacc && __builtin_amdgcn_readfirstlane(s_pub)) {
+            hacc_publish<TPB>(P.hacc, P.nhot, tid);
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
+    }
     bar_raw();
     dma_slots(0);
     keep_rotate();
@@ -1633,11 +1695,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(TPB / 128))
         // Thread t adds z (t even) or n (t odd) of entry t / 2 to ACC[t]: every wave-instruction
         // covers 256 contiguous bytes.  The non-zero test keeps a -0.0 entry bit-exact; a masked lane
         // does not widen the instruction's span.
-        if (c_hacc)
+        if (c_hacc) {
             for (int t = tid; t < 2 * P.nhot; t += TPB) {
                 const float2 d = s_hd[t >> 1];
                 if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + t, (t & 1) ? d.y : d.x);
             }
+            if (tid == 0) hacc_count_flush(P.hacc, P.nhot);   // the gate's FLUSHED
+        }
     }
 #undef SA
 #undef SB
@@ -1685,6 +1749,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     __shared__ float2 s_hd[LT ? HD12_SIZE : 1];
     __shared__ __attribute__((aligned(16))) float4 s_hacc[LT ? 2 : 1][48];
     __shared__ __attribute__((aligned(16))) int s_nh[LT ? 2 : 1][48];
+    __shared__ int s_pub;                                             // LT: this block publishes (the gate)
     const int F = P.F;
     const int FF = F * F;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1793,12 +1858,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     if (row >= P.B) return;
     if (tid == 0) { s_bcur[0] = 0.f; s_bcur[1] = 0.f; }
     dma_meta(0, row);
+    // LT: the publish gate, as in ffm_pipe_sg32_kernel
+    HaccGate gate = {0u, 0u, 0u, 0};
     if constexpr (LT != 0) {
-        if (P.hacc_on) hacc_publish<256>(P.hacc, P.nhot, tid);   // (as in ffm_pipe_sg32_kernel)
+        if (P.hacc_on && tid == 0) gate = hacc_gate_load(P.hacc, P.nhot);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
+    if constexpr (LT != 0) {
+        if (P.hacc_on && tid == 0) {
+            const bool open = hacc_gate_open(gate);
+            s_pub = open;
+            if (open) hacc_gate_mark(P.hacc, P.nhot, gate);
+        }
+    }
     bar_raw();
     publish_meta(0);
+    if constexpr (LT != 0) {
+        if (P.hacc_on && __builtin_amdgcn_readfirstlane(s_pub)) {
+            hacc_publish<256>(P.hacc, P.nhot, tid);
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+        }
+    }
     bar_raw();
     dma_slots(0);
     keep_rotate();
@@ -2016,11 +2096,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void f
     __builtin_amdgcn_s_waitcnt(0x0F70);       // no LDS-DMA outstanding at exit
     if constexpr (LT != 0) {
         bar_raw();   // (as in ffm_pipe_sg32_kernel)
-        if (P.hacc_on)
+        if (P.hacc_on) {
             for (int t = tid; t < 2 * P.nhot; t += 256) {
                 const float2 d = s_hd[t >> 1];
                 if (d.y != 0.f || d.x != 0.f) atomicAdd(P.hacc + t, (t & 1) ? d.y : d.x);
             }
+            if (tid == 0) hacc_count_flush(P.hacc, P.nhot);
+        }
     }
 #undef SA
 #undef SB
@@ -2095,6 +2177,8 @@ int dispatch_lean(const FFMParams& P, const FFMArgs& a, int grid, hipStream_t st
 // before a launch, dir 1 folds ACC back into the records (w = f(z, n)) after it.
 __global__ __launch_bounds__(256) void ffm_hacc_kernel(FFMParams P, float* __restrict__ w, int dir) {
     const int h = blockIdx.x * 256 + threadIdx.x;
+    // dir 0 also zeroes the publish gate's counters, FLUSHED and SEEN[8] (hacc_ctl_off; EVERY stays)
+    if (dir == 0 && h <= 8) reinterpret_cast<uint32_t*>(P.hacc + hacc_ctl_off(P.nhot))[HACC_CTL_LINE * h] = 0u;
     if (h >= P.nhot) return;
     float4* rp = reinterpret_cast<float4*>(&LW(w, P.hot_id[h]));
     float2* ap = reinterpret_cast<float2*>(P.hacc) + h;

@@ -227,7 +227,9 @@ _LIN_DEFER = int(os.environ.get("HM_FFM_LIN_DEFER", "1") != "0")
 #     (csrc/kernels/ffm.hip ffm_hacc_kernel).  The table is two tables in one allocation: ACC, 8-B
 #     {z, n} entries, contiguous, the atomics' only target (a flush instruction covers 256
 #     contiguous bytes); and READ, 16-B {z, n, 0, 0} entries on a 128-B line behind it, which the
-#     rows read and every block refreshes from ACC when it starts.  No atomic lands on READ, so
+#     rows read and a starting block refreshes from ACC when its XCD has not yet seen
+#     HACC_PUBLISH_EVERY of the launch's flushes (below): READ lags ACC by fewer than that many
+#     flushes chip-wide plus the flushes in flight.  No atomic lands on READ, so
 #     none drops the lines the rows read from L2: that is what the earlier one-entry-per-line
 #     layout of a single table paid for (csrc/kernels/ffm.hip, HD_SIZE).
 #   0: plain record stores (a concurrent row's step to the same feature is lost)
@@ -238,7 +240,7 @@ _LIN_DEFER = int(os.environ.get("HM_FFM_LIN_DEFER", "1") != "0")
 LIN_MODES = (0, 4)
 _LIN_ATOMIC = int(os.environ.get("HM_FFM_LIN_ATOMIC", "4"))
 _LIN_HOT_N = min(int(os.environ.get("HM_FFM_LIN_HOT", "2048")), 2048)   # <= HD_SIZE of the kernel
-_LIN_HOT: dict = {}   # (device, w.data_ptr(), NF, H) -> (hidx int32 [NF], hot_id int32 [H], hacc f32 (ACC | READ), [launches])
+_LIN_HOT: dict = {}   # (device, w.data_ptr(), NF, H) -> (hidx int32 [NF], hot_id int32 [H], hacc f32 (ACC | READ | gate control), [launches])
 _LIN_HOT_KEEP = 8     # states whose tables are kept (4 MB index each at 2^20 features); an evicted
                       # state rebuilds its table from its next batch (its records hold the folded
                       # state after every launch, so nothing is lost)
@@ -257,6 +259,33 @@ def _hacc_views(hacc: torch.Tensor, nhot: int):
     """(ACC [nhot, 2], READ [nhot, 4]) of a side-table allocation: {z, n} and {z, n, 0, 0}."""
     off = _hacc_read_off(nhot)
     return hacc[:2 * nhot].view(nhot, 2), hacc[off:off + 4 * nhot].view(nhot, 4)
+
+
+# The publish gate (csrc/kernels/ffm.hip, hacc_ctl_off): a starting block copies ACC to READ only
+# when at least this many block flushes have been counted since its XCD's last publish.  1 skips
+# only the copies that cannot change READ (the whole first round of blocks among them); 0 = every
+# block publishes, the behaviour before round 11.  HM_FFM_HACC_EVERY: A/B and test handle.  The
+# value is written into a table's control block when the table is created.
+# Measured (docs/perf_notes.md round 11, one box, alternating): fp32 92.7 M rows/s before, 92.8 /
+# 93.2 / 95.1 / 95.5 / 95.7 M at T = 1 / 8 / 64 / 256 / 512; bf16 132.7 M before, 137.6 / 138.2 /
+# 138.4 M at 64 / 256 / 512.  64 is the largest of them whose held-out logloss gap stays inside the
+# parent's own run-to-run range for both kernels (bf16 at 256 and 512: +0.05e-3 .. +0.1e-3 outside).
+HACC_PUBLISH_EVERY = int(os.environ.get("HM_FFM_HACC_EVERY", "64"))
+_HACC_CTL_LINE = 32          # floats per 128-B line: one uint32 per line
+_HACC_CTL_LINES = 10         # FLUSHED, SEEN[8], EVERY
+
+
+def _hacc_ctl_off(nhot: int) -> int:
+    """The control block's offset in the side-table allocation, in floats: behind READ's 4 nhot, on
+    a 128-B line of its own (hacc_ctl_off of csrc/kernels/ffm.hip)."""
+    return (_hacc_read_off(nhot) + 4 * nhot + 31) & ~31
+
+
+def _hacc_ctl(hacc: torch.Tensor, nhot: int):
+    """(FLUSHED [1], SEEN [8], EVERY [1]) of a side-table allocation, int32 views (uint32 counters)."""
+    off = _hacc_ctl_off(nhot)
+    c = hacc[off:off + _HACC_CTL_LINE * _HACC_CTL_LINES].view(torch.int32).view(_HACC_CTL_LINES, _HACC_CTL_LINE)[:, 0]
+    return c[0:1], c[1:9], c[9:10]
 
 
 def _lin_hot_tables(state: dict, idx: torch.Tensor, nhot: int):
@@ -280,7 +309,8 @@ def _lin_hot_tables(state: dict, idx: torch.Tensor, nhot: int):
         hidx = torch.full((nf,), -1, dtype=torch.int32, device=w.device)
         hidx[top.long()] = torch.arange(top.numel(), dtype=torch.int32, device=w.device)
         n = max(1, top.numel())
-        hacc = torch.zeros(_hacc_read_off(n) + 4 * n, dtype=torch.float32, device=w.device)
+        hacc = torch.zeros(_hacc_ctl_off(n) + _HACC_CTL_LINE * _HACC_CTL_LINES, dtype=torch.float32, device=w.device)
+        _hacc_ctl(hacc, n)[2].fill_(HACC_PUBLISH_EVERY)
         while len(_LIN_HOT) >= _LIN_HOT_KEEP:        # the oldest states' tables go first
             _LIN_HOT.pop(next(iter(_LIN_HOT)))
         t = _LIN_HOT[key] = (hidx, top, hacc, [0])
