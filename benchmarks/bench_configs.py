@@ -92,7 +92,7 @@ def bench_linear_hashed(dev="cuda", n_rows=8 * 262144, bits=24, epochs=2):
                     eidx.reshape(-1).contiguous(), None, None)
     ll = torch.nn.functional.binary_cross_entropy_with_logits(m.decision_function(rows=er),
                                                               (ey > 0).float()).item()
-    eng = "shared-table Hogwild" if m.state.meta.get("shared") else f"{m.state.R} replicas"
+    eng = "shared-table Hogwild" if m.state.engine == "shared" else f"{m.state.R} replicas"
     return {"config": f"train_classifier adagrad logistic, Criteo-shaped {n_rows} x 39 nnz, -dims 2^{bits}",
             "device": dev, "engine": eng, "rows_per_s": round(n_rows * (epochs - 1) / dt),
             "heldout_logloss_after_epochs": round(ll, 5), "epochs": epochs}

@@ -39,8 +39,7 @@ def fit(opts, rows, test, dev):
     dt = time.perf_counter() - t
     s = m.decision_function(rows=test.to(dev)).cpu()
     ll = torch.nn.functional.binary_cross_entropy_with_logits(s, (test.y > 0).float()).item()
-    eng = ("minibatch" if m.state.meta.get("minibatch") else
-           "shared" if m.state.meta.get("shared") else f"replica{m.state.R}")
+    eng = m.state.engine if m.state.engine in ("minibatch", "shared") else f"replica{m.state.R}"
     del m
     if dev == "cuda":
         torch.cuda.empty_cache()

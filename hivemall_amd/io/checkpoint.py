@@ -30,6 +30,8 @@ import torch
 
 _SCALARS = ("t", "rows_seen", "num_features", "num_fields", "dims", "n_users", "n_items", "labels",
             "classes", "k", "kp", "grid", "K", "dp_power", "dp_guard_tripped")
+# the named scalar fields of ops/linear.py LinearState, saved as ``state_meta``
+_LINEAR_SCALARS = ("engine", "reload", "nt", "spread", "touched_cap")
 
 
 def _collect_tensors(learner) -> dict:
@@ -87,6 +89,7 @@ def save(learner, path: str, model_table: bool = True) -> str:
         tensors = {k: v.detach().cpu() for k, v in _collect_tensors(learner).items()}
         torch.save(tensors, os.path.join(tmp, "state.pt"))
         st = getattr(learner, "state", None)
+        from ..ops.linear import LinearState
         meta = {
             "class": f"{type(learner).__module__}:{type(learner).__qualname__}",
             "name": getattr(learner, "NAME", None),
@@ -94,10 +97,10 @@ def save(learner, path: str, model_table: bool = True) -> str:
             "scalars": {k: _jsonable(getattr(learner, k)) for k in _SCALARS
                         if hasattr(learner, k) and isinstance(getattr(learner, k), (int, float, str, list, tuple, type(None), np.integer, np.floating))},
             "state_kind": "dataclass" if dataclasses.is_dataclass(st) else ("dict" if isinstance(st, dict) else None),
-            # JSON scalars only: tensors kept in meta are scratch buffers the engines rebuild
-            # (ops/linear.py train_pass_minibatch), caches (the hot set) are recomputed
-            "state_meta": ({k: v for k, v in st.meta.items() if isinstance(v, (bool, int, float, str))}
-                           if dataclasses.is_dataclass(st) and hasattr(st, "meta") else None),
+            # the linear state's engine and launch scalars; its ``scratch`` (buffers and caches
+            # the engines rebuild, ops/linear.py) is not saved
+            "state_meta": ({k: getattr(st, k) for k in _LINEAR_SCALARS}
+                           if isinstance(st, LinearState) else None),
             "state_covar": bool(getattr(st, "covar", False)) if dataclasses.is_dataclass(st) else None,
             "encoder": _encoder_meta(getattr(learner, "encoder", None)),
             "cv": vars(learner.cv) if hasattr(learner, "cv") else None,
@@ -205,8 +208,13 @@ def load(path: str, device=None, restore_rng: bool = False, **kw):
             learner.state = st_t
     elif kind == "dataclass":
         from ..ops.linear import LinearState
+        sm = dict(meta.get("state_meta") or {})
+        # checkpoints from before ``engine`` was a field flag their engine: "shared": true, ...
+        legacy = [e for e in ("shared", "seq", "minibatch") if sm.pop(e, False)]
+        sm.setdefault("engine", legacy[0] if legacy else "replica")
         learner.state = LinearState(st_t["S"], st_t["touched"], st_t["RS"], bool(meta["state_covar"]),
-                                    st_t.get("gacc"), st_t.get("tlist"), meta.get("state_meta") or {})
+                                    st_t.get("gacc"), st_t.get("tlist"),
+                                    **{k: sm[k] for k in _LINEAR_SCALARS if k in sm})
     for k, v in tensors.items():
         if k.startswith("attr."):
             setattr(learner, k[5:], v.to(dev))

@@ -361,88 +361,52 @@ class OnlineLinearLearner(Learner):
             raise UDFArgumentException(f"{self.NAME}: needs at least two distinct labels")
         self.P.n_labels = L
         R = self._auto_replicas(rows.n)
-        mb = int(self.cl["mini_batch"]) if self.ALGO == "general" else 1
-        if self._use_minibatch(L, mb):
-            nnz = int((rows.indptr[1:] - rows.indptr[:-1]).max().item()) if rows.n else 1
-            self.state = LO.new_minibatch_state(dims, self.device, mb, nnz)
-            if self._warm is not None:
-                self.load_model_table(self._warm)
-            return
-        if self._use_seq(L, mb):
-            W = int(self.cl["shared_waves"]) or LO.seq_waves(self.P)
-            if int(self.cl["seq_spread"]) not in (1, 8):
-                raise UDFArgumentException(f"{self.NAME}: -seq_spread must be 1 or 8")
-            self.state = LO.new_seq_state(dims, self.device, max(1, min(W, max(1, rows.n))),
-                                          int(self.cl["seq_spread"]))
-            if self._warm is not None:
-                self.load_model_table(self._warm)
-            return
-        if self._use_shared(R, L, dims, mb):
-            try:
-                W = LO.shared_waves(rows.n, int(self.cl["shared_waves"]) or LO.rule_waves(self.P))
-                if W <= 16 and rows.n > 64 * W:
-                    log.warning("%s: the shared-table engine runs this rule with %d rows in flight "
-                                "(~%d M rows/s on one MI355X); -engine seq keeps the rows in flight "
-                                "on one XCD at 128-512 rows (ops/linear.py seq_waves)",
-                                self.NAME, W, max(1, W // 4))
-                # at a few rows in flight the read-modify-write window is no hazard: skip the
-                # state re-read before the update (+5 % at 8 rows, same parity:
-                # profiles/r4/linear_reload_ab_8rows.jsonl)
-                self.state = LO.new_shared_state(
-                    dims, self.device, rows.n, replicas=int(self.cl["shared_replicas"]), waves=W,
-                    reload=W > 16)
-            except ValueError as e:
-                raise UDFArgumentException(f"{self.NAME}: {e}") from None
-            if self._warm is not None:
-                self.load_model_table(self._warm)
-            return
-        bytes_ = R * L * dims * 16
-        if bytes_ > (32 << 30):
-            R = max(1, (32 << 30) // (L * dims * 16))
-        self.state = LO.new_state(R, L, dims, self.device, self.covar, self.P.init_covar, mb)
+        mb = self._mini_batch()
+        self.state = self._new_state(self._engine(R, L, dims, mb), rows, R, L, dims, mb)
         if self._warm is not None:
             self.load_model_table(self._warm)
 
-    def _use_minibatch(self, L: int, mb: int) -> bool:
-        """Mini-batch engine (``-mini_batch M > 1`` of the general learner on a GPU, one table,
-        the whole chip on each batch; ops/linear.py train_pass_minibatch): the default for
-        -mini_batch > 1 unless -engine replica / -replicas ask for per-wave replicas."""
-        eng = str(self.cl["engine"]).lower()
-        if eng == "minibatch":
-            if not (self.device.type == "cuda" and mb > 1 and L == 1 and LO.minibatch_rule(self.P)):
-                raise UDFArgumentException(f"{self.NAME}: -engine minibatch needs a GPU, -mini_batch > 1, "
-                                           "a binary/regression general learner and -opt other than eve")
-            return True
-        return (eng == "auto" and int(self.cl["replicas"]) <= 0 and self.device.type == "cuda"
-                and mb > 1 and L == 1 and LO.minibatch_rule(self.P))
+    def _mini_batch(self) -> int:
+        return int(self.cl["mini_batch"]) if self.ALGO == "general" else 1
 
-    def _use_seq(self, L: int, mb: int) -> bool:
-        """Near-sequential engine (ops/linear.py train_pass_seq): ``-engine seq``, or auto for the
-        general-learner rules whose parity needs few rows in flight (ops/linear.py seq_rule)."""
-        eng = str(self.cl["engine"]).lower()
-        ok = self.device.type == "cuda" and not self.covar and L == 1 and mb == 1
-        if eng == "seq":
-            if not ok:
-                raise UDFArgumentException(f"{self.NAME}: -engine seq needs a GPU, a rule without "
-                                           "covariance, a binary/regression task and -mini_batch 1")
-            return True
-        return (eng == "auto" and ok and int(self.cl["replicas"]) <= 0
-                and int(self.cl["shared_replicas"]) == 1 and LO.seq_rule(self.P))
+    def _engine(self, R: int, L: int, dims: int, mb: int) -> str:
+        """The engine of ``-engine`` for this learner's rule (ops/linear.py choose_engine)."""
+        try:
+            return LO.choose_engine(
+                self.P, self.cl["engine"], on_gpu=self.device.type == "cuda", covar=self.covar,
+                n_labels=L, mini_batch=mb, replicas=int(self.cl["replicas"]),
+                shared_replicas=int(self.cl["shared_replicas"]), auto_replicas=R, dims=dims)
+        except ValueError as e:
+            raise UDFArgumentException(f"{self.NAME}: {e}") from None
 
-    def _use_shared(self, R: int, L: int, dims: int, mb: int) -> bool:
-        """Shared-table Hogwild engine: device only, binary/regression rules
-        without covariance, per-row updates.  auto picks it when R private replicas of
-        ``dims x 16 B`` would exceed 2 GiB (e.g. Hivemall's default 2^24 hashed dims)."""
-        eng = str(self.cl["engine"]).lower()
-        if eng not in ("auto", "replica", "shared", "minibatch", "seq"):
-            raise UDFArgumentException(f"{self.NAME}: -engine must be auto, replica, shared, seq or minibatch")
-        ok = (self.device.type == "cuda" and not self.covar and L == 1 and mb == 1)
-        if eng == "shared" and not ok:
-            raise UDFArgumentException(f"{self.NAME}: -engine shared needs a GPU, a rule without "
-                                       "covariance, a binary/regression task and -mini_batch 1")
-        if eng == "replica" or not ok or int(self.cl["replicas"]) > 0:
-            return eng == "shared"
-        return eng == "shared" or R * dims * 16 > (2 << 30)
+    def _new_state(self, engine: str, rows: SparseRows, R: int, L: int, dims: int, mb: int) -> LO.LinearState:
+        if engine == "minibatch":
+            nnz = int((rows.indptr[1:] - rows.indptr[:-1]).max().item()) if rows.n else 1
+            return LO.new_minibatch_state(dims, self.device, mb, nnz)
+        if engine == "seq":
+            W = int(self.cl["shared_waves"]) or LO.seq_waves(self.P)
+            if int(self.cl["seq_spread"]) not in (1, 8):
+                raise UDFArgumentException(f"{self.NAME}: -seq_spread must be 1 or 8")
+            return LO.new_seq_state(dims, self.device, max(1, min(W, max(1, rows.n))),
+                                    int(self.cl["seq_spread"]))
+        if engine == "shared":
+            W = LO.shared_waves(rows.n, int(self.cl["shared_waves"]) or LO.rule_waves(self.P))
+            if W <= 16 and rows.n > 64 * W:
+                log.warning("%s: the shared-table engine runs this rule with %d rows in flight "
+                            "(~%d M rows/s on one MI355X); -engine seq keeps the rows in flight "
+                            "on one XCD at 128-512 rows (ops/linear.py seq_waves)",
+                            self.NAME, W, max(1, W // 4))
+            # at a few rows in flight the read-modify-write window is no hazard: skip the
+            # state re-read before the update (+5 % at 8 rows, same parity:
+            # profiles/r4/linear_reload_ab_8rows.jsonl)
+            try:
+                return LO.new_shared_state(dims, self.device, rows.n, waves=W,
+                                           replicas=int(self.cl["shared_replicas"]), reload=W > 16)
+            except ValueError as e:
+                raise UDFArgumentException(f"{self.NAME}: {e}") from None
+        if R * L * dims * 16 > (32 << 30):
+            R = max(1, (32 << 30) // (L * dims * 16))
+        return LO.new_state(R, L, dims, self.device, self.covar, self.P.init_covar, mb)
 
     # ------------------------------------------------------------------ training
     def fit(self, features=None, labels=None, rows: SparseRows | None = None) -> "OnlineLinearLearner":
@@ -452,24 +416,10 @@ class OnlineLinearLearner(Learner):
         self._ensure_state(rows)
         if rows.idx.numel() and int(tmax(rows.idx)) >= self.state.dims:
             log.warning("%s: feature index >= dims (%d) ignored", self.NAME, self.state.dims)
-        mb = int(self.cl["mini_batch"]) if self.ALGO == "general" else 1
-        iters = int(self.cl["iters"])
-        shared = self.state.meta.get("shared", False)
-        minibatch = self.state.meta.get("minibatch", False)
-        seq = self.state.meta.get("seq", False)
-        for ep in self.epochs(iters, data=(rows.indptr, rows.idx, rows.val, rows.y)):
-            if seq:
-                loss = LO.train_pass_seq(self.state, self.P, rows.indptr, rows.idx, rows.val, rows.y,
-                                         self.rows_seen)
-            elif minibatch:
-                loss = LO.train_pass_minibatch(self.state, self.P, rows.indptr, rows.idx, rows.val, rows.y,
-                                               self.rows_seen, mb)
-            elif shared:
-                loss = LO.train_pass_shared(self.state, self.P, rows.indptr, rows.idx, rows.val, rows.y,
-                                            self.rows_seen)
-            else:
-                loss = LO.train_pass(self.state, self.P, rows.indptr, rows.idx, rows.val, rows.y,
-                                     None, mb)
+        mb = self._mini_batch()
+        for ep in self.epochs(int(self.cl["iters"]), data=(rows.indptr, rows.idx, rows.val, rows.y)):
+            loss = LO.train_rows(self.state, self.P, rows.indptr, rows.idx, rows.val, rows.y,
+                                 self.rows_seen, mb)
             self.rows_seen += rows.n
             self.mix()
             if self.epoch_converged(float(loss.sum().item()), rows=rows.n):

@@ -13,6 +13,7 @@ import ctypes as C
 import os
 import weakref
 from dataclasses import dataclass, field
+from types import MappingProxyType
 
 import numpy as np
 import torch
@@ -56,15 +57,34 @@ class LinParams(C.Structure):
                                  "beta_hd", "scale", "quantile_tau", "huber_c", "init_covar")]
 
 
+ENGINES = ("replica", "shared", "seq", "minibatch")
+
+
 @dataclass
 class LinearState:
     S: torch.Tensor
     touched: torch.Tensor
     RS: torch.Tensor
     covar: bool
-    gacc: torch.Tensor | None = None
-    tlist: torch.Tensor | None = None
-    meta: dict = field(default_factory=dict)
+    gacc: torch.Tensor | None = None     # replica engine, -mini_batch > 1: gradient sums [R, dims, 2]
+    tlist: torch.Tensor | None = None    # ... and the batch's feature list [R, touched_cap]
+    engine: str = "replica"              # one of ENGINES: which train_pass* runs the state
+    reload: bool = False                 # shared: re-read the state before the update
+    nt: bool = True                      # shared / seq: model read with non-temporal loads
+    spread: int = 8                      # seq: 8 = every wave on one XCD, 1 = dealt over all
+    touched_cap: int = 0                 # replica: entries of tlist per replica
+    # rebuilt on demand, never checkpointed: the mini-batch engine's buffers (ga, mark, list,
+    # cnt), the owner-mode accumulators (hacc) and the hot-set cache (hot)
+    scratch: dict = field(default_factory=dict)
+
+    @property
+    def meta(self):
+        """The fields above as the dict of magic keys they replaced (the engine as a true flag,
+        the launch scalars, scratch's entries), for readers written against that layout.  An
+        immutable mapping: assigning into it raises instead of being lost."""
+        flag = {} if self.engine == "replica" else {self.engine: True}
+        return MappingProxyType({**flag, "reload": self.reload, "nt": self.nt, "spread": self.spread,
+                                 "touched_cap": self.touched_cap, **self.scratch})
 
     @property
     def R(self) -> int:
@@ -83,55 +103,64 @@ class LinearState:
         return self.S.device
 
 
+def _zero_state(R: int, L: int, dims: int, W: int, device, covar: bool = False, **fields) -> LinearState:
+    """Zeroed S [R, L, dims, 4], touched [R, dims] and scalars RS [W, 8]."""
+    return LinearState(torch.zeros((R, L, dims, 4), dtype=torch.float32, device=device),
+                       torch.zeros((R, dims), dtype=torch.uint8, device=device),
+                       torch.zeros((W, 8), dtype=torch.float32, device=device), covar, **fields)
+
+
+def _alloc_batch_lists(st: LinearState) -> None:
+    """The replica kernel's mini-batch buffers: per-replica gradient sums and feature list."""
+    st.touched_cap = max(64 * 8, min(st.dims, 1 << 22))
+    st.gacc = torch.zeros((st.R, st.dims, 2), dtype=torch.float32, device=st.device)
+    st.tlist = torch.zeros((st.R, st.touched_cap), dtype=torch.int32, device=st.device)
+
+
 def new_state(R: int, L: int, dims: int, device, covar: bool, init_covar: float = 1.0,
               mini_batch: int = 1) -> LinearState:
-    S = torch.zeros((R, L, dims, 4), dtype=torch.float32, device=device)
+    st = _zero_state(R, L, dims, R, device, covar, engine="replica")
     if covar:
-        S[..., 1] = init_covar
-    st = LinearState(S, torch.zeros((R, dims), dtype=torch.uint8, device=device),
-                     torch.zeros((R, 8), dtype=torch.float32, device=device), covar)
-    if mini_batch > 1 and S.is_cuda:
-        st.gacc = torch.zeros((R, dims, 2), dtype=torch.float32, device=device)
-        cap = max(64 * 8, min(dims, 1 << 22))
-        st.tlist = torch.zeros((R, cap), dtype=torch.int32, device=device)
-        st.meta["touched_cap"] = cap
+        st.S[..., 1] = init_covar
+    if mini_batch > 1 and st.S.is_cuda:
+        _alloc_batch_lists(st)
     return st
 
 
-def _ip(st: LinearState, mini_batch: int) -> np.ndarray:
-    return np.array([st.R, st.dims, st.L, mini_batch, st.meta.get("touched_cap", 0)], dtype=np.int32)
-
-
-def train_pass(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.Tensor,
-               val: torch.Tensor | None, y: torch.Tensor, order: torch.Tensor | None = None,
-               mini_batch: int = 1) -> torch.Tensor:
-    """One pass over the rows (each replica over its shard).  Returns per-replica loss sums."""
+def _check_rows(st: LinearState, indptr, idx, val, y, order, engine: str = "replica") -> int:
+    """The argument checks of every train_pass*: the state is ``engine``'s (a device engine
+    unless it is the replica engine) and the rows are contiguous tensors of the kernels' types
+    on the state's device.  Returns the row count."""
     n = indptr.numel() - 1
-    dev = st.device
+    assert st.engine == engine, f"not a {engine} engine state"
+    assert engine == "replica" or st.device.type == "cuda", f"the {engine} engine is a device engine"
     for t in (indptr, idx, val, y, order):
         if t is not None:
-            assert t.device == dev and t.is_contiguous(), "tensor device/layout mismatch"
+            assert t.device == st.device and t.is_contiguous(), "tensor device/layout mismatch"
     assert indptr.dtype == torch.int64 and idx.dtype == torch.int32 and y.dtype == torch.float32
     assert y.numel() >= n
     if val is not None:
         assert val.dtype == torch.float32 and val.numel() == idx.numel()
     if order is not None:
         assert order.dtype == torch.int32 and order.numel() == n
+    return n
+
+
+def train_pass(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.Tensor,
+               val: torch.Tensor | None, y: torch.Tensor, order: torch.Tensor | None = None,
+               mini_batch: int = 1) -> torch.Tensor:
+    """One pass over the rows (each replica over its shard).  Returns per-replica loss sums."""
+    n = _check_rows(st, indptr, idx, val, y, order)
+    dev = st.device
+    if dev.type == "cuda" and mini_batch > 1 and st.gacc is None:
+        _alloc_batch_lists(st)
     loss = torch.zeros(st.R, dtype=torch.float64, device=dev)
-    ip = _ip(st, mini_batch)
+    ip = np.array([st.R, st.dims, st.L, mini_batch, st.touched_cap], dtype=np.int32)
     p = _native.ptr
     args = [C.addressof(P), ip.ctypes.data, C.c_int64(n), p(indptr), p(idx), p(val), p(y), p(order),
             p(st.S), p(st.touched), p(st.RS), p(loss)]
     if dev.type == "cuda":
-        if mini_batch > 1 and st.gacc is None:
-            st.gacc = torch.zeros((st.R, st.dims, 2), dtype=torch.float32, device=dev)
-            cap = max(64 * 8, min(st.dims, 1 << 22))
-            st.tlist = torch.zeros((st.R, cap), dtype=torch.int32, device=dev)
-            st.meta["touched_cap"] = cap
-            ip = _ip(st, mini_batch)
-            args[1] = ip.ctypes.data
-        rc = _native.hip().hm_linear_train(*args, p(st.gacc), p(st.tlist), _native.stream_of(dev))
-        _native.check(rc, "hm_linear_train")
+        _native.call_hip("hm_linear_train", dev, *args, p(st.gacc), p(st.tlist))
     else:
         _native.call_host("hm_linear_train", *args)
     return loss
@@ -161,13 +190,8 @@ def new_shared_state(dims: int, device, n_rows: int, waves: int | None = None, r
     if R != 1 and (R % 8 or (W + 3) // 4 < R):
         raise ValueError(f"shared engine: replicas must be 1 or a multiple of 8 with >= 4 * R waves "
                          f"(R={R}, W={W})")
-    st = LinearState(torch.zeros((R, 1, dims, 4), dtype=torch.float32, device=device),
-                     torch.zeros((R, dims), dtype=torch.uint8, device=device),
-                     torch.zeros((W, 8), dtype=torch.float32, device=device), False)
-    st.meta["shared"] = True
-    st.meta["reload"] = bool(int(os.environ.get("HM_LINEAR_RELOAD", int(reload))))
-    st.meta["nt"] = bool(nt)
-    return st
+    return _zero_state(R, 1, dims, W, device, engine="shared", nt=bool(nt),
+                       reload=bool(int(os.environ.get("HM_LINEAR_RELOAD", int(reload)))))
 
 
 HOT_MAX = 4096          # <= csrc/kernels/linear.hip HM_HOT_MAX; 48 KB of LDS accumulators
@@ -268,6 +292,50 @@ def rule_waves(P: LinParams) -> int:
     return SHARED_WAVES
 
 
+def minibatch_rule(P: LinParams) -> bool:
+    """Rules of the mini-batch engine: the general learner, one label, any optimizer but Eve
+    (whose per-row loss feedback is a sequential chain, not a batch rule)."""
+    return P.algo == ALGOS["general"] and P.n_labels == 1 and P.opt != OPTIMIZERS["eve"]
+
+
+def choose_engine(P: LinParams, engine: str, *, on_gpu: bool, covar: bool, n_labels: int,
+                  mini_batch: int, replicas: int, shared_replicas: int, auto_replicas: int,
+                  dims: int) -> str:
+    """The engine (one of ENGINES) that runs rule ``P`` under ``-engine engine``; ValueError for
+    a name or a combination that is refused.
+
+    The mini-batch engine (one table, the whole chip on each batch) needs a GPU, -mini_batch > 1
+    and a rule of ``minibatch_rule``; the shared-table and near-sequential engines (one table,
+    per-row updates) need a GPU, no covariance, one label and -mini_batch 1.  ``auto`` keeps
+    per-wave replicas when ``-replicas`` asks for them, and otherwise picks the mini-batch engine
+    where it can run, then the seq engine for the rules of ``seq_rule`` (unless
+    ``-shared_replicas`` asks for several shared tables), then the shared table when
+    ``auto_replicas`` private tables of ``dims x 16 B`` would exceed 2 GiB (e.g. Hivemall's
+    default 2^24 hashed dims)."""
+    eng = str(engine).lower()
+    if eng != "auto" and eng not in ENGINES:
+        raise ValueError("-engine must be auto, replica, shared, seq or minibatch")
+    batch_ok = on_gpu and mini_batch > 1 and n_labels == 1 and minibatch_rule(P)
+    table_ok = on_gpu and not covar and n_labels == 1 and mini_batch == 1
+    if eng == "minibatch" and not batch_ok:
+        raise ValueError("-engine minibatch needs a GPU, -mini_batch > 1, a binary/regression "
+                         "general learner and -opt other than eve")
+    if eng in ("shared", "seq") and not table_ok:
+        raise ValueError(f"-engine {eng} needs a GPU, a rule without covariance, a "
+                         "binary/regression task and -mini_batch 1")
+    if eng != "auto":
+        return eng
+    if replicas > 0:
+        return "replica"
+    if batch_ok:
+        return "minibatch"
+    if not table_ok:
+        return "replica"
+    if shared_replicas == 1 and seq_rule(P):
+        return "seq"
+    return "shared" if auto_replicas * dims * 16 > (2 << 30) else "replica"
+
+
 def hot_features(st: LinearState, P: LinParams, idx: torch.Tensor, n_rows: int):
     """The features the shared-table kernel pre-aggregates per block instead of updating them
     Hogwild (csrc/kernels/linear.hip, HOT): the at most ``HOT_MAX`` most frequent features of
@@ -279,7 +347,7 @@ def hot_features(st: LinearState, P: LinParams, idx: torch.Tensor, n_rows: int):
     # keyed on the tensor object itself (weakly) and its version counter: a later pass whose
     # index tensor happens to land at a freed address must not reuse this pass's hot set
     key = (idx.numel(), st.dims, n_rows, idx._version)
-    hit = st.meta.get("hot")
+    hit = st.scratch.get("hot")
     if hit is not None and hit[0]() is idx and hit[1] == key:
         return hit[2]
     W = st.RS.shape[0]
@@ -298,7 +366,7 @@ def hot_features(st: LinearState, P: LinParams, idx: torch.Tensor, n_rows: int):
         slot = torch.full((st.dims,), -1, dtype=torch.int32, device=idx.device)
         slot[feats.long()] = torch.arange(feats.numel(), dtype=torch.int32, device=idx.device)
         res = (slot, feats.contiguous())
-    st.meta["hot"] = (weakref.ref(idx), key, res)
+    st.scratch["hot"] = (weakref.ref(idx), key, res)
     return res
 
 
@@ -307,14 +375,8 @@ def train_pass_shared(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: 
                       order: torch.Tensor | None = None) -> torch.Tensor:
     """One Hogwild pass of the shared tables over the rows; step of row q = t0 + q + 1.  Returns
     per-wave loss sums."""
-    n = indptr.numel() - 1
+    n = _check_rows(st, indptr, idx, val, y, order, "shared")
     dev = st.device
-    assert dev.type == "cuda", "the shared-table engine is a device engine"
-    assert indptr.dtype == torch.int64 and idx.dtype == torch.int32 and y.dtype == torch.float32
-    assert y.numel() >= n and (val is None or val.numel() == idx.numel())
-    for t in (indptr, idx, val, y, order):
-        if t is not None:
-            assert t.device == dev and t.is_contiguous(), "tensor device/layout mismatch"
     W = st.RS.shape[0]
     loss = torch.zeros(W, dtype=torch.float64, device=dev)
     p = _native.ptr
@@ -322,9 +384,9 @@ def train_pass_shared(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: 
     hs, hf, H = (hot[0], hot[1], hot[1].numel()) if hot is not None else (None, None, 0)
     hacc = None
     if H and not hot_rule(P):                 # owner mode: zeroed [H] accumulators (re-zeroed by the pass)
-        hacc = st.meta.get("hacc")
+        hacc = st.scratch.get("hacc")
         if hacc is None or hacc.shape[0] < H:
-            hacc = st.meta["hacc"] = torch.zeros((max(H, HOT_MAX), 4), dtype=torch.float32, device=dev)
+            hacc = st.scratch["hacc"] = torch.zeros((max(H, HOT_MAX), 4), dtype=torch.float32, device=dev)
     # rows per wave per chunk: HOT_CHUNK, or fewer so that a short pass still has >= 32 chunk
     # ends at which the hot features' sums are applied
     ch = int(os.environ.get("HM_LINEAR_HOT_CH", max(1, min(HOT_CHUNK, n // max(1, W * 32)))))
@@ -335,14 +397,10 @@ def train_pass_shared(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: 
     # one huge step at the end (held-out logloss 0.61-0.67 vs the sequential 0.479-0.487)
     nchunks = -(-n // max(1, W * ch))
     hevery = int(os.environ.get("HM_LINEAR_HOT_EVERY", max(1, min(HOT_EVERY, nchunks // 16))))
-    rc = _native.hip().hm_linear_train_shared(C.addressof(P), C.c_int64(n), st.dims, C.c_int64(int(t0)), W,
-                                              st.R, int(st.meta.get("reload", False)),
-                                              int(st.meta.get("nt", True)),
-                                              p(indptr), p(idx), p(val), p(y), p(order), p(st.S),
-                                              p(st.touched), p(st.RS), p(loss), p(hs), p(hf), H, ch, hmin, hevery,
-                                              p(hacc),
-                                              _native.stream_of(dev))
-    _native.check(rc, "hm_linear_train_shared")
+    _native.call_hip("hm_linear_train_shared", dev, C.addressof(P), C.c_int64(n), st.dims,
+                     C.c_int64(int(t0)), W, st.R, int(st.reload), int(st.nt), p(indptr), p(idx), p(val),
+                     p(y), p(order), p(st.S), p(st.touched), p(st.RS), p(loss), p(hs), p(hf), H, ch,
+                     hmin, hevery, p(hacc))
     return loss
 
 
@@ -350,11 +408,7 @@ def new_seq_state(dims: int, device, waves: int, spread: int = 8) -> LinearState
     """Near-sequential engine state (csrc/kernels/linear.hip linear_seq_kernel): one table
     S [1, 1, dims, 4], touched [1, dims], per-wave scalars RS [W, 8]; ``spread`` 8 keeps the W
     waves on one XCD (1: dealt over all of them)."""
-    st = LinearState(torch.zeros((1, 1, dims, 4), dtype=torch.float32, device=device),
-                     torch.zeros((1, dims), dtype=torch.uint8, device=device),
-                     torch.zeros((int(waves), 8), dtype=torch.float32, device=device), False)
-    st.meta.update(seq=True, spread=int(spread), nt=True)
-    return st
+    return _zero_state(1, 1, dims, int(waves), device, engine="seq", spread=int(spread), nt=True)
 
 
 def train_pass_seq(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.Tensor,
@@ -362,44 +416,33 @@ def train_pass_seq(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: tor
                    order: torch.Tensor | None = None) -> torch.Tensor:
     """One pass of the near-sequential engine (row q on wave q % W, step t0 + q + 1).  Returns
     per-wave loss sums."""
-    n = indptr.numel() - 1
-    dev = st.device
-    assert dev.type == "cuda" and st.meta.get("seq"), "near-sequential engine state on a GPU"
-    assert indptr.dtype == torch.int64 and idx.dtype == torch.int32 and y.dtype == torch.float32
-    assert y.numel() >= n and (val is None or val.numel() == idx.numel())
-    for t in (indptr, idx, val, y, order):
-        if t is not None:
-            assert t.device == dev and t.is_contiguous(), "tensor device/layout mismatch"
+    n = _check_rows(st, indptr, idx, val, y, order, "seq")
     W = st.RS.shape[0]
-    loss = torch.zeros(W, dtype=torch.float64, device=dev)
+    loss = torch.zeros(W, dtype=torch.float64, device=st.device)
     p = _native.ptr
-    rc = _native.hip().hm_linear_train_seq(C.addressof(P), C.c_int64(n), st.dims, C.c_int64(int(t0)), W,
-                                           int(st.meta.get("spread", 8)), int(st.meta.get("nt", True)),
-                                           p(indptr), p(idx), p(val), p(y), p(order), p(st.S),
-                                           p(st.touched), p(st.RS), p(loss), _native.stream_of(dev))
-    _native.check(rc, "hm_linear_train_seq")
+    _native.call_hip("hm_linear_train_seq", st.device, C.addressof(P), C.c_int64(n), st.dims,
+                     C.c_int64(int(t0)), W, int(st.spread), int(st.nt), p(indptr), p(idx), p(val), p(y),
+                     p(order), p(st.S), p(st.touched), p(st.RS), p(loss))
     return loss
+
+
+def _batch_buffers(st: LinearState, cap: int) -> None:
+    """The mini-batch engine's zeroed scratch (every batch leaves it zeroed): gradient sums,
+    touched marks, two list counters and the batch's feature list of at least ``cap`` entries.
+    Builds what is missing, e.g. all of it on a state restored from a checkpoint."""
+    for k, shape, dt in (("ga", st.dims, torch.float32), ("mark", st.dims, torch.int32),
+                         ("cnt", 2, torch.int32), ("list", cap, torch.int32)):
+        t = st.scratch.get(k)
+        if t is None or t.device != st.device or (k == "list" and t.numel() < cap):
+            st.scratch[k] = torch.zeros(shape, dtype=dt, device=st.device)
 
 
 def new_minibatch_state(dims: int, device, max_rows_per_batch: int, max_nnz: int) -> LinearState:
     """Mini-batch engine state (csrc/kernels/linear.hip hm_linear_train_minibatch): one table
-    S [1, 1, dims, 4] plus the batch buffers (gradient sums, touched marks, the batch's feature
-    list and two list counters), all zeroed."""
-    st = LinearState(torch.zeros((1, 1, dims, 4), dtype=torch.float32, device=device),
-                     torch.zeros((1, dims), dtype=torch.uint8, device=device),
-                     torch.zeros((1, 8), dtype=torch.float32, device=device), False)
-    cap = int(min(dims, max(1, max_rows_per_batch) * max(1, max_nnz)))
-    st.meta.update(minibatch=True, ga=torch.zeros(dims, dtype=torch.float32, device=device),
-                   mark=torch.zeros(dims, dtype=torch.int32, device=device),
-                   list=torch.zeros(cap, dtype=torch.int32, device=device),
-                   cnt=torch.zeros(2, dtype=torch.int32, device=device))
+    S [1, 1, dims, 4] plus the batch buffers, all zeroed."""
+    st = _zero_state(1, 1, dims, 1, device, engine="minibatch")
+    _batch_buffers(st, int(min(dims, max(1, max_rows_per_batch) * max(1, max_nnz))))
     return st
-
-
-def minibatch_rule(P: LinParams) -> bool:
-    """Rules of the mini-batch engine: the general learner, one label, any optimizer but Eve
-    (whose per-row loss feedback is a sequential chain, not a batch rule)."""
-    return P.algo == ALGOS["general"] and P.n_labels == 1 and P.opt != OPTIMIZERS["eve"]
 
 
 def train_pass_minibatch(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.Tensor,
@@ -407,33 +450,29 @@ def train_pass_minibatch(st: LinearState, P: LinParams, indptr: torch.Tensor, id
                          order: torch.Tensor | None = None) -> torch.Tensor:
     """One pass of the mini-batch engine (batches of M rows in order; row q's step t0 + q + 1).
     Returns the pass's loss sum (device, [1])."""
-    n = indptr.numel() - 1
-    dev = st.device
-    assert dev.type == "cuda" and st.meta.get("minibatch"), "mini-batch engine state on a GPU"
-    assert indptr.dtype == torch.int64 and idx.dtype == torch.int32 and y.dtype == torch.float32
-    for t in (indptr, idx, val, y, order):
-        if t is not None:
-            assert t.device == dev and t.is_contiguous(), "tensor device/layout mismatch"
-    # the batch buffers are zeroed scratch (every batch leaves them zeroed): a state restored from
-    # a checkpoint (io/checkpoint.py keeps only JSON scalars of state.meta) gets fresh ones
-    for k, shape, dt in (("ga", (st.dims,), torch.float32), ("mark", (st.dims,), torch.int32),
-                         ("cnt", (2,), torch.int32), ("list", (1,), torch.int32)):
-        if not isinstance(st.meta.get(k), torch.Tensor) or st.meta[k].device != dev:
-            st.meta[k] = torch.zeros(shape, dtype=dt, device=dev)
-    if n > 0:
-        nnz = int((indptr[1:] - indptr[:-1]).max().item())
-        need = min(st.dims, M * max(1, nnz))
-        if st.meta["list"].numel() < need:
-            st.meta["list"] = torch.zeros(need, dtype=torch.int32, device=dev)
-    loss = torch.zeros(1, dtype=torch.float64, device=dev)
+    n = _check_rows(st, indptr, idx, val, y, order, "minibatch")
+    nnz = int((indptr[1:] - indptr[:-1]).max().item()) if n > 0 else 0
+    _batch_buffers(st, min(st.dims, M * max(1, nnz)) if n > 0 else 1)
+    loss = torch.zeros(1, dtype=torch.float64, device=st.device)
     p = _native.ptr
-    rc = _native.hip().hm_linear_train_minibatch(C.addressof(P), C.c_int64(n), st.dims, C.c_int64(int(t0)), int(M),
-                                                 p(indptr), p(idx), p(val), p(y), p(order), p(st.S),
-                                                 p(st.touched), p(st.meta["ga"]), p(st.meta["mark"]),
-                                                 p(st.meta["list"]), p(st.meta["cnt"]), p(loss),
-                                                 _native.stream_of(dev))
-    _native.check(rc, "hm_linear_train_minibatch")
+    sc = st.scratch
+    _native.call_hip("hm_linear_train_minibatch", st.device, C.addressof(P), C.c_int64(n), st.dims,
+                     C.c_int64(int(t0)), int(M), p(indptr), p(idx), p(val), p(y), p(order), p(st.S),
+                     p(st.touched), p(sc["ga"]), p(sc["mark"]), p(sc["list"]), p(sc["cnt"]), p(loss))
     return loss
+
+
+def train_rows(st: LinearState, P: LinParams, indptr: torch.Tensor, idx: torch.Tensor,
+               val: torch.Tensor | None, y: torch.Tensor, t0: int, mini_batch: int = 1,
+               order: torch.Tensor | None = None) -> torch.Tensor:
+    """One pass of the state's engine over the rows, ``t0`` rows after the start of training.
+    Returns the engine's loss sums (per replica, per wave, or one)."""
+    if st.engine == "replica":        # its step counters live in RS
+        return train_pass(st, P, indptr, idx, val, y, order, mini_batch)
+    if st.engine == "minibatch":
+        return train_pass_minibatch(st, P, indptr, idx, val, y, t0, mini_batch, order)
+    run = {"shared": train_pass_shared, "seq": train_pass_seq}[st.engine]
+    return run(st, P, indptr, idx, val, y, t0, order)
 
 
 def mix_reduce(st: LinearState, kld: bool):
@@ -444,10 +483,8 @@ def mix_reduce(st: LinearState, kld: bool):
         num = torch.empty(L * dims, dtype=torch.float32, device=dev)
         den = torch.empty_like(num)
         cnt = torch.empty_like(num)
-        rc = _native.hip().hm_linear_mix_reduce(_native.ptr(st.S), _native.ptr(st.touched), R, dims,
-                                                L, int(kld), _native.ptr(num), _native.ptr(den),
-                                                _native.ptr(cnt), _native.stream_of(dev))
-        _native.check(rc, "hm_linear_mix_reduce")
+        _native.call_hip("hm_linear_mix_reduce", dev, _native.ptr(st.S), _native.ptr(st.touched), R, dims,
+                         L, int(kld), _native.ptr(num), _native.ptr(den), _native.ptr(cnt))
         return num, den, cnt
     t = st.touched.to(torch.float32).view(R, 1, dims)          # [R,1,dims]
     w = st.S[..., 0]
@@ -469,11 +506,9 @@ def mix_apply(st: LinearState, kld: bool, num, den, cnt):
     w_out = torch.empty(L * dims, dtype=torch.float32, device=dev)
     cov_out = torch.empty_like(w_out) if st.covar else None
     if dev.type == "cuda":
-        rc = _native.hip().hm_linear_mix_apply(_native.ptr(st.S), R, dims, L, int(kld),
-                                               _native.ptr(num), _native.ptr(den), _native.ptr(cnt),
-                                               _native.ptr(w_out), _native.ptr(cov_out),
-                                               _native.stream_of(dev))
-        _native.check(rc, "hm_linear_mix_apply")
+        _native.call_hip("hm_linear_mix_apply", dev, _native.ptr(st.S), R, dims, L, int(kld),
+                         _native.ptr(num), _native.ptr(den), _native.ptr(cnt), _native.ptr(w_out),
+                         _native.ptr(cov_out))
         return w_out.view(L, dims), (cov_out.view(L, dims) if cov_out is not None else None)
     num, den, cnt = (x.view(L, dims) for x in (num, den, cnt))
     hit = cnt > 0
@@ -501,13 +536,11 @@ def predict_scores(w: torch.Tensor, indptr: torch.Tensor, idx: torch.Tensor,
     p = _native.ptr
     w = w.contiguous()
     cov = cov.contiguous() if cov is not None else None
+    args = (p(w), dims, L, p(indptr), p(idx), p(val), C.c_int64(n), p(out), p(cov), p(var))
     if dev.type == "cuda":
-        rc = _native.hip().hm_linear_predict(p(w), dims, L, p(indptr), p(idx), p(val), C.c_int64(n),
-                                             p(out), p(cov), p(var), _native.stream_of(dev))
-        _native.check(rc, "hm_linear_predict")
+        _native.call_hip("hm_linear_predict", dev, *args)
     else:
-        _native.host().hm_linear_predict_cpu(p(w), dims, L, p(indptr), p(idx), p(val), C.c_int64(n),
-                                             p(out), p(cov), p(var))
+        _native.call_host("hm_linear_predict", *args)
     return out, var
 
 

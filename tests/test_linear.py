@@ -198,11 +198,11 @@ def test_shared_engine_selection_rules():
     """auto keeps replicas on CPU / for covariance rules; -engine shared is refused where the
     shared-table kernel cannot run."""
     m = L.TrainClassifier("-loss logloss -dims 16777216", device="cpu")
-    assert not m._use_shared(1, 1, 1 << 24, 1)
+    assert m._engine(1, 1, 1 << 24, 1) == "replica"
     with pytest.raises(UDFArgumentException):
-        L.TrainClassifier("-engine shared", device="cpu")._use_shared(1, 1, 100, 1)
+        L.TrainClassifier("-engine shared", device="cpu")._engine(1, 1, 100, 1)
     with pytest.raises(UDFArgumentException):
-        L.TrainClassifier("-engine bogus", device="cpu")._use_shared(1, 1, 100, 1)
+        L.TrainClassifier("-engine bogus", device="cpu")._engine(1, 1, 100, 1)
 
 
 @pytest.mark.gpu
@@ -258,7 +258,7 @@ def test_gpu_seq_engine_one_wave_is_sequential(opts, spread):
 
 @pytest.mark.gpu
 def test_gpu_minibatch_engine_resumes_from_checkpoint(tmp_path):
-    """the mini-batch engine's batch buffers are scratch tensors in state.meta, which
+    """the mini-batch engine's batch buffers are scratch tensors in state.scratch, which
     the checkpoint does not keep; a restored learner rebuilds them and trains on."""
     from hivemall_amd.io import checkpoint as ck
 
@@ -266,10 +266,10 @@ def test_gpu_minibatch_engine_resumes_from_checkpoint(tmp_path):
     m = L.TrainClassifier("-loss logloss -opt adam -eta0 0.01 -dims 1048576 -iters 1 -mini_batch 256",
                           device="cuda")
     m.fit(rows=rows)
-    assert m.state.meta.get("minibatch")
+    assert m.state.engine == "minibatch"
     ck.save(m, str(tmp_path / "ck"))
     m2 = ck.load(str(tmp_path / "ck"), device="cuda")
-    assert m2.state.meta.get("minibatch") and not isinstance(m2.state.meta.get("ga"), torch.Tensor)
+    assert m2.state.engine == "minibatch" and not isinstance(m2.state.scratch.get("ga"), torch.Tensor)
     m.fit(rows=rows)
     m2.fit(rows=rows)
     torch.cuda.synchronize()
@@ -315,13 +315,13 @@ def test_gpu_shared_engine_hashed_2p24_logloss_parity(opts):
         m.fit(rows=rows.to(dev))
         if dev == "cuda":
             if LO.seq_rule(m.P):
-                assert m.state.meta.get("seq") and m.state.meta["spread"] == 8
+                assert m.state.engine == "seq" and m.state.spread == 8
                 assert m.state.RS.shape[0] == LO.seq_waves(m.P)
             else:
                 W = LO.rule_waves(m.P)
-                assert m.state.meta.get("shared") and m.state.RS.shape[0] == W
+                assert m.state.engine == "shared" and m.state.RS.shape[0] == W
                 if LO.hot_rule(m.P) or LO.hot_owner_rule(m.P):
-                    assert m.state.meta["hot"][2] is not None and m.state.meta["hot"][2][1].numel() > 100
+                    assert m.state.scratch["hot"][2] is not None and m.state.scratch["hot"][2][1].numel() > 100
             seq = LO.seq_rule(m.P)
         s = m.decision_function(rows=test.to(dev)).cpu()
         res[dev] = torch.nn.functional.binary_cross_entropy_with_logits(s, yy).item()
@@ -348,7 +348,7 @@ def test_gpu_minibatch_engine_matches_sequential_minibatch_learner(opts):
         m = L.TrainClassifier(f"-loss logloss {opts} -dims 16777216 -iters 2 -disable_cv -mini_batch 1024", device=dev)
         m.fit(rows=rows.to(dev))
         if dev == "cuda":
-            assert m.state.meta.get("minibatch")
+            assert m.state.engine == "minibatch"
         s = m.decision_function(rows=test.to(dev)).cpu()
         res[dev] = torch.nn.functional.binary_cross_entropy_with_logits(s, yy).item()
         ws[dev] = m.weights()[0][0].cpu()
@@ -369,11 +369,214 @@ def test_seq_engine_routing_table():
               "eve", "adam_hd", "adagrad"):
         m = L.TrainClassifier(f"-loss logloss -opt {o}", device="cpu")
         waves[o] = LO.seq_waves(m.P) if LO.seq_rule(m.P) else None
-        assert not m._use_seq(1, 1)                   # CPU device
+        assert m._engine(1, 1, 1 << 24, 1) == "replica"   # CPU device: neither seq nor shared
     assert waves["adagrad"] is None
     assert waves["sgd"] == waves["rmsprop"] == waves["adadelta"] == waves["momentum"] == 512
     assert waves["adam"] == waves["nadam"] == waves["adam_hd"] == waves["rmspropgraves"] == 256
     assert waves["eve"] == 128
     assert LO.seq_rule(L.TrainClassifier("-loss logloss -opt adagrad -reg l1", device="cpu").P) is False
     with pytest.raises(UDFArgumentException):
-        L.TrainClassifier("-engine seq", device="cpu")._use_seq(1, 1)
+        L.TrainClassifier("-engine seq", device="cpu")._engine(1, 1, 100, 1)
+
+
+# ---------------------------------------------------------------------------- engine routing
+@pytest.fixture
+def default_routing(monkeypatch):
+    """The routing knobs at their defaults, whatever the environment of the test run."""
+    from hivemall_amd.ops import linear as LO
+
+    for k in ("HM_LINEAR_HOT", "HM_LINEAR_HOT_OWNER"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(LO, "_SEQ_AUTO", True)
+
+
+def _route(name, opts="", engine="auto", on_gpu=True, n_labels=1, mini_batch=1, replicas=0, shared_replicas=1,
+           auto_replicas=1024, dims=1 << 24):
+    """ops/linear.py choose_engine for the rule of learner ``name`` with ``opts``; "error" when
+    the combination is refused."""
+    from hivemall_amd.ops import linear as LO
+
+    m = L.LEARNERS[name](opts, device="cpu")
+    m.P.n_labels = n_labels
+    try:
+        return LO.choose_engine(m.P, engine, on_gpu=on_gpu, covar=m.covar, n_labels=n_labels,
+                                mini_batch=mini_batch, replicas=replicas, shared_replicas=shared_replicas,
+                                auto_replicas=auto_replicas, dims=dims)
+    except ValueError:
+        return "error"
+
+
+def test_engine_routing_matches_recorded_table(default_routing):
+    """Every row of tests/golden/linear_routing.json: the decisions of the three order-dependent
+    predicates that choose_engine replaced, recorded over the full product of -engine (every name,
+    one in upper case, one unknown) x GPU / CPU x rule class (AdaGrad: hot sums; AdaGrad-L1: owner
+    mode; SGD and Eve: seq-routed, Eve refused by the mini-batch engine; train_pa1: not general;
+    train_arow: covariance) x binary / 3 labels x -mini_batch 1 / 256 (general learner) x
+    -replicas 0 / 4 x -shared_replicas 1 / 8 x (auto replicas, dims) below and above 2 GiB."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "linear_routing.json")) as f:
+        table = json.load(f)
+    assert len(table["rows"]) == 1344
+    bad = []
+    for row in table["rows"]:
+        r = dict(zip(table["columns"], row))
+        want, name, opts = r.pop("outcome"), r.pop("learner"), r.pop("opts")
+        got = _route(name, opts, **r)
+        if got != want:
+            bad.append((row, got))
+    assert not bad, bad[:10]
+
+
+_SGD, _ADAGRAD = "-loss logloss -opt sgd", "-loss logloss -opt adagrad -reg no"
+ROUTES = {  # id: (learner, options, choose_engine arguments, outcome); a GPU, 1,024 x 2^24 unless said
+    "auto-adagrad-large-tables-share": ("train_classifier", _ADAGRAD, {}, "shared"),
+    "auto-adagrad-l1-shares-too": ("train_classifier", "-loss logloss -opt adagrad -reg l1", {}, "shared"),
+    "auto-adagrad-under-2GiB-keeps-replicas": ("train_classifier", _ADAGRAD, {"auto_replicas": 1}, "replica"),
+    "auto-sgd-is-seq-at-any-size": ("train_classifier", _SGD, {"auto_replicas": 1}, "seq"),
+    "auto-shared_replicas-keeps-off-seq": ("train_classifier", _SGD, {"shared_replicas": 8}, "shared"),
+    "auto-replicas-option-keeps-replicas": ("train_classifier", _SGD, {"replicas": 4}, "replica"),
+    "auto-mini_batch-is-minibatch": ("train_classifier", _SGD, {"mini_batch": 256}, "minibatch"),
+    "auto-mini_batch-with-replicas": ("train_classifier", _SGD, {"mini_batch": 256, "replicas": 4}, "replica"),
+    "auto-mini_batch-eve-keeps-replicas": ("train_classifier", "-loss logloss -opt eve", {"mini_batch": 256},
+                                           "replica"),
+    "minibatch-refuses-eve": ("train_classifier", "-loss logloss -opt eve",
+                              {"engine": "minibatch", "mini_batch": 256}, "error"),
+    "minibatch-needs-mini_batch": ("train_classifier", _SGD, {"engine": "minibatch"}, "error"),
+    "named-engine-beats-replicas": ("train_classifier", _SGD,
+                                    {"engine": "minibatch", "mini_batch": 256, "replicas": 4}, "minibatch"),
+    "seq-refuses-mini_batch": ("train_classifier", _SGD, {"engine": "seq", "mini_batch": 256}, "error"),
+    "auto-covariance-keeps-replicas": ("train_arow", "", {}, "replica"),
+    "shared-refuses-covariance": ("train_arow", "", {"engine": "shared"}, "error"),
+    "auto-not-general-shares": ("train_pa1", "", {}, "shared"),
+    "auto-multiclass-keeps-replicas": ("train_multiclass_pa1", "", {"n_labels": 3}, "replica"),
+    "seq-refuses-multiclass": ("train_multiclass_pa1", "", {"engine": "seq", "n_labels": 3}, "error"),
+    "replica-by-name": ("train_classifier", _SGD, {"engine": "replica"}, "replica"),
+    "name-is-lower-cased": ("train_classifier", _ADAGRAD, {"engine": "SEQ"}, "seq"),
+    "unknown-name": ("train_classifier", _ADAGRAD, {"engine": "bogus"}, "error"),
+    "unknown-name-on-cpu": ("train_classifier", _ADAGRAD, {"engine": "bogus", "on_gpu": False}, "error"),
+    "cpu-auto-keeps-replicas": ("train_classifier", _SGD, {"on_gpu": False}, "replica"),
+    "cpu-refuses-shared": ("train_classifier", _ADAGRAD, {"engine": "shared", "on_gpu": False}, "error"),
+}
+
+
+@pytest.mark.parametrize("rid", list(ROUTES))
+def test_engine_routing_rules(default_routing, rid):
+    name, opts, kw, want = ROUTES[rid]
+    assert _route(name, opts, **kw) == want
+
+
+def test_engine_routing_errors_name_the_learner():
+    """A refused combination is a ValueError of choose_engine without the learner's name; the
+    learner raises it as UDFArgumentException with its name in front, an unknown -engine first."""
+    from hivemall_amd.ops import linear as LO
+
+    m = L.TrainClassifier("-engine bogus -mini_batch 4", device="cpu")
+    with pytest.raises(ValueError, match="^-engine must be auto, replica, shared, seq or minibatch$"):
+        LO.choose_engine(m.P, "bogus", on_gpu=False, covar=False, n_labels=1, mini_batch=4, replicas=0,
+                         shared_replicas=1, auto_replicas=1, dims=100)
+    with pytest.raises(UDFArgumentException, match="^train_classifier: -engine must be auto"):
+        m._engine(1, 1, 100, 4)
+    rows = _criteo_rows(10, 8, seed=1)
+    for eng, opts in (("shared", ""), ("seq", ""), ("minibatch", "-mini_batch 4")):
+        with pytest.raises(UDFArgumentException, match=f"^train_classifier: -engine {eng} needs a GPU"):
+            L.TrainClassifier(f"-engine {eng} {opts}", device="cpu").fit(rows=rows)
+
+
+# ---------------------------------------------------------------------------- engine state and checkpoints
+_STATE_FIELDS = ("engine", "reload", "nt", "spread", "touched_cap")
+# what a checkpoint from before LinearState.engine kept per engine, beside the engine's flag
+_LEGACY_KEYS = {"replica": ("touched_cap",), "shared": ("reload", "nt"), "seq": ("spread", "nt"), "minibatch": ()}
+
+
+def _engine_state(engine, device="cpu"):
+    from hivemall_amd.ops import linear as LO
+
+    if engine == "replica":
+        st = LO.new_state(2, 1, 64, device, False)
+        st.touched_cap = 512
+    elif engine == "shared":
+        st = LO.new_shared_state(64, device, 100, waves=3, reload=True, nt=False)
+        st.scratch.update(hacc=torch.zeros(4, 4), hot=(None, (), None))
+    elif engine == "seq":
+        st = LO.new_seq_state(64, device, waves=3, spread=1)
+    else:
+        st = LO.new_minibatch_state(64, device, 4, 3)
+        assert {"ga", "mark", "list", "cnt"} <= set(st.scratch)
+    assert st.engine == engine
+    return st
+
+
+@pytest.mark.parametrize("engine", ["replica", "shared", "seq", "minibatch"])
+def test_engine_state_survives_checkpoint(tmp_path, engine, monkeypatch):
+    """The state's engine and launch scalars are saved by name and restored; nothing of scratch is
+    saved; a checkpoint in the earlier form (engine flags, no "engine") loads to the same state."""
+    import json
+
+    from hivemall_amd.io import checkpoint as ck
+
+    monkeypatch.delenv("HM_LINEAR_RELOAD", raising=False)
+    m = L.TrainClassifier("-loss logloss -dims 64", device="cpu")
+    m.state = st = _engine_state(engine)
+    st.S.copy_(torch.arange(st.S.numel(), dtype=torch.float32).view_as(st.S))
+    want = {k: getattr(st, k) for k in _STATE_FIELDS}
+    assert want["engine"] == engine
+    # the immutable view in the earlier layout: the engine as a flag, the scalars, scratch's entries
+    flag = {} if engine == "replica" else {engine: True}
+    assert dict(st.meta) == {**flag, **{k: want[k] for k in _STATE_FIELDS[1:]}, **st.scratch}
+    with pytest.raises(TypeError):
+        st.meta["reload"] = True
+    path = str(tmp_path / "ck")
+    ck.save(m, path)
+    saved = torch.load(f"{path}/state.pt", weights_only=True)
+    assert {k for k in saved if k.startswith("state.")} == {"state.S", "state.touched", "state.RS"}
+
+    def check():
+        st2 = ck.load(path, device="cpu").state
+        assert {k: getattr(st2, k) for k in _STATE_FIELDS} == want
+        assert all(type(getattr(st2, k)) is type(want[k]) for k in _STATE_FIELDS)
+        assert st2.scratch == {} and st2.covar is False
+        assert torch.equal(st2.S, st.S) and st2.RS.shape == st.RS.shape
+
+    check()
+    with open(f"{path}/meta.json") as f:
+        meta = json.load(f)
+    assert meta["state_meta"] == want
+    legacy = {k: want[k] for k in _LEGACY_KEYS[engine]}
+    if engine != "replica":
+        legacy[engine] = True
+    meta["state_meta"] = legacy
+    with open(f"{path}/meta.json", "w") as f:
+        json.dump(meta, f)
+    check()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("engine,opts", [("shared", "-engine shared -shared_waves 1"),
+                                         ("seq", "-engine seq -shared_waves 1"),
+                                         ("minibatch", "-engine minibatch -mini_batch 64"),
+                                         ("replica", "-engine replica -replicas 1")])
+def test_gpu_engine_through_learner_resumes_from_checkpoint(tmp_path, engine, opts):
+    """Each engine through the learner (routing, state, train_rows dispatch) at the smallest shape:
+    3,000 rows with distinct features per row, one wave or one replica, so a pass is deterministic
+    and a restored learner must train on to the very same weights (the mini-batch engine's
+    gradient sums are atomic: the existing resume test's tolerance)."""
+    from hivemall_amd.io import checkpoint as ck
+
+    rows = _criteo_rows(3000, 12, seed=3, distinct=True).to("cuda")
+    m = L.TrainClassifier(f"-loss logloss -dims 4096 -iters 1 {opts}", device="cuda")
+    m.fit(rows=rows)
+    assert m.state.engine == engine
+    ck.save(m, str(tmp_path / "ck"))
+    m2 = ck.load(str(tmp_path / "ck"), device="cuda")
+    assert m2.state.engine == engine and m2.state.scratch == {}
+    m.fit(rows=rows)
+    m2.fit(rows=rows)
+    torch.cuda.synchronize()
+    w1, w2 = m.weights()[0].cpu(), m2.weights()[0].cpu()
+    assert w1.abs().max() > 0
+    if engine == "minibatch":
+        assert torch.allclose(w1, w2, rtol=1e-4, atol=1e-6)
+    else:
+        assert torch.equal(w1, w2)

@@ -692,7 +692,7 @@ def test_gpu_minibatch_engine_matches_oracle(opt, M):
     for ep in range(2):
         loss += LO.train_pass_minibatch(st, m.P, f.indptr, f.idx, f.val, f.y[case.task], t0=ep * n, M=M).item()
     check(st.S[0, 0].cpu().numpy(), st.touched[0].cpu().numpy(), None, loss, ref, case.id)
-    assert not st.meta["ga"].any() and not st.meta["mark"].any()      # the batch buffers are left zeroed
+    assert not st.scratch["ga"].any() and not st.scratch["mark"].any()      # the batch buffers are left zeroed
 
 
 # ---------------------------------------------------------------------------- GPU: mix kernels
