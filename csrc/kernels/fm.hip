@@ -42,7 +42,9 @@ struct FMParams {
     uint32_t seed;
     const uint8_t* hot;       // per-feature flags (nullable): a hot feature's V row / w stores go
                               // out SC1 (write-through, dropped from the writer's XCD L2) ...
-    uint32_t hot_mask;        // ... on the rows whose hash & hot_mask == 0 (0: every row)
+    uint32_t hot_mask;        // ... on the rows whose hash & hot_mask == 0 (0: every row).  Only the
+                              // first 64 non-zeros of a row are looked up: later chunks of a wide
+                              // row always store plainly
     int xcds;                 // fm_pipe_kernel: waves on this many of the 8 XCDs (8: all; fewer:
                               // only blocks with blockIdx % 8 < xcds work — round-robin placement)
     long long vstride;        // V elements between feature rows (>= KP)
@@ -452,14 +454,20 @@ __global__ __launch_bounds__(256) void fm_pipe_kernel(FMParams P, const int64_t*
         if (P.train) {
             const float eta = fm_eta(P, (float)(t0 + row + 1));
             const uint32_t rbase = P.seed ^ (uint32_t)(t0 + row) * 0x9E3779B9u;
-            auto upd = [&](VRow<KP, BF16>& t, int ii, float xx, float ww) {
+            // the step of one feature is computed once and only the store instruction is chosen
+            // afterwards (sc1), so a hot feature's result has the bits of the plain path's
+            auto upd = [&](VRow<KP, BF16>& t, int ii, float xx, float ww, bool sc1) {
                 const float nw = ww - eta * (d * xx + 2.f * P.lambda_w * ww);
 #pragma unroll
                 for (int f = 0; f < KP; ++f) {
                     const float g = d * xx * (S[f] - t.v[f] * xx) + 2.f * P.lambda_v * t.v[f];
                     t.v[f] = f < P.k ? t.v[f] - eta * g : 0.f;
                 }
-                if constexpr (WT > 0) {
+                if (WT > 0 || sc1) {
+                    // WT: every store; else a hot feature (P.hot): the store leaves through to
+                    // memory and drops the line from this XCD's L2, so the next read of it on this
+                    // XCD fetches the other XCDs' updates instead of this XCD's stale copy
+                    // (docs/perf_notes.md round 6)
                     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(nw), wrs,
                                                           (uint32_t)((size_t)ii * P.wstride * 4), 0, CPOL_SC1);
                     t.store_sc1(vrs, ii, P.vstride, rbase);
@@ -468,24 +476,7 @@ __global__ __launch_bounds__(256) void fm_pipe_kernel(FMParams P, const int64_t*
                     t.store(V, ii, P.vstride, rbase);
                 }
             };
-            if (i >= 0) {
-                if (hotf) {
-                    // a hot feature (P.hot): the store leaves through to memory and drops the line
-                    // from this XCD's L2, so the next read of it on this XCD fetches the other XCDs'
-                    // updates instead of this XCD's stale copy (docs/perf_notes.md round 6)
-                    const float nw = wi - eta * (d * x + 2.f * P.lambda_w * wi);
-#pragma unroll
-                    for (int f = 0; f < KP; ++f) {
-                        const float g = d * x * (S[f] - vr.v[f] * x) + 2.f * P.lambda_v * vr.v[f];
-                        vr.v[f] = f < P.k ? vr.v[f] - eta * g : 0.f;
-                    }
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(nw), wrs,
-                                                          (uint32_t)((size_t)i * P.wstride * 4), 0, CPOL_SC1);
-                    vr.store_sc1(vrs, i, P.vstride, rbase);
-                } else {
-                    upd(vr, i, x, wi);
-                }
-            }
+            if (i >= 0) upd(vr, i, x, wi, hotf);
             for (int base = 64; base < nnz; base += 64) {
                 const int j = base + lane;
                 if (j >= nnz) continue;
@@ -494,7 +485,7 @@ __global__ __launch_bounds__(256) void fm_pipe_kernel(FMParams P, const int64_t*
                 const float x2 = val ? val[s + j] : 1.f;
                 VRow<KP, BF16> t;
                 t.load(V, i2, P.vstride);
-                upd(t, i2, x2, FW(i2));
+                upd(t, i2, x2, FW(i2), false);
             }
             if (P.use_w0) {
                 const float dw0 = -eta * (d + 2.f * P.lambda0 * w0v);
