@@ -13,7 +13,14 @@ itself: ``ops.knn_sparse``); ``SLIM.fit`` (the SQL surface) groups the rows as u
 hands them over.  ``torch`` is the batched torch descent over
 NumPy Gram matrices, ``slim_cd_batched``, the reference the native engine is tested against.
 Both are fp64 throughout and follow the update and coordinate order of upstream's residual
-loop.  ``train_kpa`` is a small per-example sequential learner and runs on the host.
+loop.
+
+``train_kpa`` is a per-example sequential learner with two engines (``-engine auto|native|python``).
+``python`` is the per-row loop over dicts below, the definition.  ``native`` is ``ops.kpa``: a
+whole-chip pair-table kernel, a one-workgroup sequential PA-I trainer and a scoring kernel
+(``csrc/kernels/kpa.hip``), or their C++ twin on a CPU device (``csrc/host/kpa_cpu.cpp``, the loop
+bit for bit).  ``auto`` takes the kernels on a ``cuda`` device and the loop everywhere else; an input
+the engine declines (``docs/compat.md``, KPA engine) stays with the loop.
 """
 from __future__ import annotations
 
@@ -339,6 +346,9 @@ KPA_OPTS = [
     opt("pkc", None, 1.0, float, "Constant c of the polynomial kernel (x·x' + c)^2"),
     opt("c", "aggressiveness", 1.0, float, "PA-I aggressiveness"),
     opt("iters", "iterations", 1, int, "Epochs"),
+    opt("engine", None, "auto", str, "[engine] native (pair-table, sequential PA-I and scoring kernels, "
+        "ops/kpa.py; their C++ twin on a CPU device) | python (the per-row loop) | auto (native on a "
+        "cuda device when its library loads and the input is inside its limits, python elsewhere)"),
 ]
 
 
@@ -354,9 +364,49 @@ class KPA(Learner):
     NAME = "train_kpa"
     OPTIONS = KPA_OPTS
 
+    def engine(self) -> str:
+        e = str(self.cl["engine"]).lower()
+        if e not in ("auto", "native", "python"):
+            raise UDFArgumentException(f"{self.NAME}: -engine must be auto, native or python, got '{e}'")
+        return e
+
     def fit(self, features, labels):
+        """``-engine`` resolved per call: the native engine where it is asked for (``native``) or
+        applies (``auto`` on a cuda device), the loop for what it declines."""
+        from ..ops import kpa as K
+
+        e, c = self.engine(), self.cl
+        if e == "native" or (e == "auto" and self.device.type == "cuda" and K.available(self.device)):
+            features, labels = list(features), list(labels)
+            try:
+                if not K.available(self.device):
+                    raise K.Decline("the native library does not load")
+                self._model = K.fit(features, labels, iters=int(c["iters"]), c=float(c["c"]),
+                                    pkc=float(c["pkc"]), device=self.device)
+            except K.Decline as why:
+                if e == "native":
+                    raise UDFArgumentException(f"{self.NAME}: -engine native declines: {why}") from None
+                log.info("%s: the native engine declines (%s); -engine python", self.NAME, why)
+            else:
+                for name in ("w1", "w2", "w3"):         # filled from the tensors on first access
+                    self.__dict__.pop(name, None)
+                self.w0 = float(self._model.w0)
+                self.pkc = self._model.pkc
+                return self
+        K.STATS["python"] += 1
+        return self._fit_python(features, labels)
+
+    def __getattr__(self, name):
+        # after a native fit the weight dicts exist as tensors until something reads them
+        if name in ("w1", "w2", "w3") and "_model" in self.__dict__:
+            self.w1, self.w2, self.w3 = self._model.dicts()
+            return self.__dict__[name]
+        raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+
+    def _fit_python(self, features, labels):
         c = self.cl
         pkc = float(c["pkc"])
+        self.__dict__.pop("_model", None)
         self.w0 = 0.0
         self.w1: dict = defaultdict(float)
         self.w2: dict = defaultdict(float)
@@ -393,6 +443,8 @@ class KPA(Learner):
 
     def model_table(self) -> pd.DataFrame:
         s0, s1, s2 = self.pkc, math.sqrt(2 * self.pkc), math.sqrt(2)
+        if "_model" in self.__dict__:
+            return self._model_table_native(s0, s1, s2)
         rows = [(0, None, self.w0 * s0, None, None, None)]
         for h in self.w1:
             rows.append((h, None, None, self.w1[h] * s1, self.w2[h], None))
@@ -400,8 +452,40 @@ class KPA(Learner):
             rows.append((h, k, None, None, None, v * s2))
         return pd.DataFrame(rows, columns=["h", "hk", "w0", "w1", "w2", "w3"])
 
+    def _model_table_native(self, s0, s1, s2) -> pd.DataFrame:
+        """The frame of the loop, column by column from the tensors: bias, names in first-seen order,
+        pairs in first-seen order.  A column without a value is all None (dtype object), as the
+        loop's frame has it."""
+        m = self._model
+        names = np.array(list(m.vocab), dtype=object)
+        a, b = m.pair_ids()
+        F, S = len(names), len(a)
+        n = 1 + F + S
+        none = lambda: np.full(n, None, dtype=object)              # noqa: E731
+        nan = lambda: np.full(n, np.nan)                            # noqa: E731
+        h, hk, w0, w1, w2, w3 = none(), none(), nan(), nan(), nan(), nan()
+        h[0] = 0
+        h[1:1 + F] = names
+        h[1 + F:] = names[a]
+        hk[1 + F:] = names[b]
+        w0[0] = self.w0 * s0
+        w1[1:1 + F] = m.w1.cpu().numpy() * s1
+        w2[1:1 + F] = m.w2.cpu().numpy()
+        w3[1 + F:] = m.w3.cpu().numpy() * s2
+        cols = {"h": h if F else h.astype(np.int64), "hk": hk, "w0": w0, "w1": w1 if F else none(),
+                "w2": w2 if F else none(), "w3": w3 if S else none()}
+        return pd.DataFrame(cols, columns=["h", "hk", "w0", "w1", "w2", "w3"])
+
     def decision_function(self, features) -> np.ndarray:
-        tab = self.model_table()
+        if "_model" in self.__dict__:
+            from ..ops import kpa as K
+
+            features = list(features)
+            try:
+                return K.score(self._model, features).cpu().numpy()
+            except K.Decline as why:
+                log.info("%s: the scoring kernel declines (%s); the per-row loop serves", self.NAME, why)
+            K.STATS["python"] += 1
         out = []
         for feats in features:
             xs = [_fv(f) for f in feats]
