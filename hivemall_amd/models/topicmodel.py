@@ -10,7 +10,8 @@ E-step runs vectorised over all of them (gather of exp E[log β] columns, scatte
 document) — on the GPU it is a handful of fused torch kernels per inner iteration.  The
 vocabulary is dictionary-encoded on the host (words are strings in SQL).  LDA's E-step and, under
 ``train_plsa -engine native``, pLSA's per-document EM and P(w|z) update run as single gfx950
-kernels instead (csrc/kernels/lda.hip, csrc/kernels/plsa.hip).
+kernels instead (csrc/kernels/lda.hip, csrc/kernels/plsa.hip).  ``train_lda -engine native`` runs a
+whole mini-batch step in three launches on a transposed table (ops/lda.py).
 
 Model tables: LDA ``(label int, word string, lambda float)``; pLSA ``(label, word, prob)``.
 """
@@ -44,6 +45,9 @@ LDA_OPTS = [
     opt("eps", None, 1e-1, float, "Perplexity convergence threshold"),
     opt("mini_batch_size", "batch_size", 128, int, "Documents per mini-batch"),
     opt("max_inner_iters", None, 100, int, "[engine] E-step iteration cap"),
+    opt("engine", None, "auto", str, "[engine] native (batch-sparse E[log beta], per-document E-step and fused "
+        "M-step kernels on a [V, K] table, ops/lda.py; at most 256 topics; seeded draws) | torch (tensor ops on "
+        "the [K, V] table, the E-step kernel on a GPU) | auto (torch)"),
     opt("seed", None, -1, int, "Seed"),
 ]
 
@@ -100,7 +104,23 @@ def _flatten(rows, device):
     return t(doc), t(w), t(c)
 
 
+def _csr(rows, device):
+    """The rows flattened once: (doc_off int64 numpy [D+1], wid int32 [N], cnt f32 [N])."""
+    _, w, cnt = _flatten(rows, device)
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in rows], out=ptr[1:])
+    return ptr, w.to(torch.int32), cnt
+
+
 class LDA(Learner):
+    """Online-VB LDA.  Two engines (``-engine auto|native|torch``, ``auto`` = ``torch``):
+
+    ``torch`` keeps lambda as ``[K, V]`` and runs a mini-batch step as tensor ops over the whole
+    table around the E-step (one kernel on a GPU).  ``native`` (ops/lda.py) keeps lambda
+    transposed with its column sums for the duration of a fit and runs a step in three launches:
+    ``exp(E[log beta])`` of the batch's words only, the per-document E-step with the bound, and one
+    pass over the table for the blend and the new column sums, without float atomics.  Every
+    random draw of the native engine comes from the learner's seeded generator."""
     NAME = "train_lda"
     OPTIONS = LDA_OPTS
 
@@ -112,17 +132,40 @@ class LDA(Learner):
             raise UDFArgumentException("train_lda: -topics must be >= 1")
         self.alpha = c["alpha"] if c["alpha"] is not None else 1.0 / self.K
         self.eta = c["eta"] if c["eta"] is not None else 1.0 / self.K
+        self._engine = self.engine()
         self.vocab = _Vocab()
         self.lam: torch.Tensor | None = None
         self.t = 0
+        self.perplexities: list = []               # native engine: every epoch's perplexity
         self.gen = torch.Generator(device="cpu").manual_seed(self.seed)
+
+    def engine(self) -> str:
+        """``-engine`` resolved: "native" (ops.lda: the gfx950 kernels on a cuda device, their C++
+        twins on the CPU) or "torch".  ``auto`` is torch on every device."""
+        from ..ops import lda as L
+
+        e = str(self.cl["engine"]).lower()
+        if e not in ("auto", "native", "torch"):
+            raise UDFArgumentException(f"{self.NAME}: -engine must be auto, native or torch, got '{e}'")
+        if e == "native" and not 1 <= self.K <= L.KMAX:
+            raise UDFArgumentException(f"{self.NAME}: -engine native holds 1..{L.KMAX} topics, got {self.K}")
+        return "torch" if e == "auto" else e
+
+    def _draw(self, shape) -> torch.Tensor:
+        """Gamma(100, 100) draws on the CPU: from the learner's seeded generator under the native
+        engine, from the global RNG under the torch engine (as ever)."""
+        if self._engine == "native":
+            # torch.distributions.Gamma takes no generator; its sampler is this private function,
+            # which does
+            return torch._standard_gamma(torch.full(tuple(shape), 100.0), generator=self.gen) / 100.0
+        return torch.distributions.Gamma(100.0, 100.0).sample(tuple(shape))
 
     def _grow(self, V):
         dev = self.device
         if self.lam is None:
-            self.lam = torch.distributions.Gamma(100.0, 100.0).sample((self.K, V)).to(dev)
+            self.lam = self._draw((self.K, V)).to(dev)
         elif self.lam.shape[1] < V:
-            extra = torch.distributions.Gamma(100.0, 100.0).sample((self.K, V - self.lam.shape[1])).to(dev)
+            extra = self._draw((self.K, V - self.lam.shape[1])).to(dev)
             self.lam = torch.cat([self.lam, extra], 1)
 
     def _elog(self, x: torch.Tensor, dim: int) -> torch.Tensor:
@@ -174,11 +217,65 @@ class LDA(Learner):
         _native.check(rc, "hm_lda_estep")
         return gamma, contrib
 
+    def _fit_native(self, rows) -> "LDA":
+        """The corpus, every mini-batch's word index and ranks and the scratch buffer are built
+        once; an epoch is one upload of its gamma draws, three launches per mini-batch and one
+        read of the bound."""
+        from ..ops import lda as L
+
+        c, dev, K = self.cl, self.device, self.K
+        V = self.lam.shape[1]
+        D = c["num_docs"] if c["num_docs"] > 0 else len(rows)
+        bs = int(c["mini_batch_size"])
+        ptr, w_all, c_all = _csr(rows, dev)
+        batches = []                                # fixed slices: indexed and validated once
+        for s in range(0, len(rows), bs):
+            e = min(len(rows), s + bs)
+            a, b = int(ptr[s]), int(ptr[e])
+            if a == b:
+                continue
+            doc_off = torch.from_numpy((ptr[s:e + 1] - a).astype(np.int32)).to(dev)
+            wid, cnt = w_all[a:b], c_all[a:b]
+            L.check_doc_batch(doc_off, wid, cnt, V, op="lda")
+            perm, word_off, uniq = L.batch_index(wid, op="lda")
+            batches.append((s, e, doc_off, L.word_positions(wid, uniq), cnt, word_off, perm, uniq))
+        if not batches:
+            return self
+        scratch = L.mstep_scratch(max(b[7].numel() for b in batches), V, K, dev)
+        lamT = self.lam.T.contiguous()
+        T = lamT.sum(0, dtype=torch.float64).float()
+        total = float(c_all.sum().item())
+        alpha, eta = float(self.alpha), float(self.eta)
+        delta, cap = float(c["delta"]), int(c["max_inner_iters"])
+        prev = None
+        for ep in range(int(c["iters"])):
+            gamma0 = self._draw((len(rows), K)).to(dev)         # the epoch's draws, one upload
+            bound = torch.zeros((), dtype=torch.float64, device=dev)
+            for s, e, doc_off, wpos, cnt, word_off, perm, uniq in batches:
+                EbU = L.lda_batch_eb(uniq, lamT, T, check=False)
+                _, contrib, _, bd = L.lda_doc_estep(doc_off, wpos, cnt, EbU, gamma0[s:e], alpha, delta, cap,
+                                                    check=False)
+                bound += bd.sum()
+                rho = (c["tau0"] + self.t) ** (-c["kappa"])
+                L.lda_mstep(word_off, perm, uniq, contrib, rho, eta, D / (e - s), lamT, T, scratch, check=False)
+                self.t += 1
+            ppl = math.exp(-float(bound.item()) / max(1.0, total))      # one sync per epoch
+            log.info("train_lda epoch %d perplexity %.3f", ep + 1, ppl)
+            self.perplexities.append(ppl)
+            if prev is not None and abs(prev - ppl) < c["eps"]:
+                break
+            prev = ppl
+        self.perplexity = prev
+        self.lam = lamT.T.contiguous()
+        return self
+
     def fit(self, docs) -> "LDA":
         c = self.cl
         rows = self.vocab.encode(list(docs), add=True)
         V = len(self.vocab.words)
         self._grow(V)
+        if self._engine == "native":
+            return self._fit_native(rows)
         D = c["num_docs"] if c["num_docs"] > 0 else len(rows)
         bs = int(c["mini_batch_size"])
         prev = None
@@ -224,6 +321,18 @@ class LDA(Learner):
 
     def transform(self, docs) -> np.ndarray:
         rows = self.vocab.encode(list(docs), add=False)
+        if self._engine == "native":
+            from ..ops import lda as L
+
+            ptr, wid, cnt = _csr(rows, self.device)
+            doc_off = torch.from_numpy(ptr.astype(np.int32)).to(self.device)
+            _, _, uniq = L.batch_index(wid, op="lda")
+            lamT = self.lam.T.contiguous()
+            EbU = L.lda_batch_eb(uniq, lamT, lamT.sum(0, dtype=torch.float64).float())
+            gamma = self._draw((len(rows), self.K)).to(self.device)
+            L.lda_doc_estep(doc_off, L.word_positions(wid, uniq), cnt, EbU, gamma, float(self.alpha),
+                            float(self.cl["delta"]), int(self.cl["max_inner_iters"]))
+            return (gamma / gamma.sum(1, keepdim=True)).cpu().numpy()
         doc, w, cnt = _flatten(rows, self.device)
         expElogbeta = torch.exp(self._elog(self.lam, 1))
         gamma, _ = self.e_step(doc, w, cnt, len(rows), expElogbeta)
@@ -345,11 +454,7 @@ class PLSA(Learner):
         return pzd, q
 
     def _csr(self, rows):
-        """The rows flattened once: (doc_off int64 numpy [D+1], wid int32 [N], cnt f32 [N])."""
-        _, w, cnt = _flatten(rows, self.device)
-        ptr = np.zeros(len(rows) + 1, dtype=np.int64)
-        np.cumsum([len(r) for r in rows], out=ptr[1:])
-        return ptr, w.to(torch.int32), cnt
+        return _csr(rows, self.device)
 
     def _fit_native(self, rows) -> "PLSA":
         from ..ops import plsa as P

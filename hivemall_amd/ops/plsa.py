@@ -63,59 +63,60 @@ def _rises(off: torch.Tensor, n: int) -> bool:
             and not bool((off[1:] < off[:-1]).any()))
 
 
-def check_doc_batch(doc_off: torch.Tensor, wid: torch.Tensor, cnt: torch.Tensor, V: int) -> int:
+def check_doc_batch(doc_off: torch.Tensor, wid: torch.Tensor, cnt: torch.Tensor, V: int, op: str = "plsa") -> int:
     """Validate a mini-batch's CSR triple (dtypes, shapes, devices, ``doc_off`` rising from 0 to
-    ``N``, ``0 <= wid < V``); returns the number of documents."""
-    _args.want("plsa", doc_off, "doc_off", torch.int32, 1)
-    _args.want("plsa", wid, "wid", torch.int32, 1)
-    _args.want("plsa", cnt, "cnt", torch.float32, 1)
-    _args.same_device("plsa", (doc_off, wid, cnt), ("doc_off", "wid", "cnt"))
+    ``N``, ``0 <= wid < V``); returns the number of documents.  ``op`` prefixes the messages (ops.lda shares
+    these checks)."""
+    _args.want(op, doc_off, "doc_off", torch.int32, 1)
+    _args.want(op, wid, "wid", torch.int32, 1)
+    _args.want(op, cnt, "cnt", torch.float32, 1)
+    _args.same_device(op, (doc_off, wid, cnt), ("doc_off", "wid", "cnt"))
     N = wid.numel()
     if cnt.numel() != N:
-        raise ValueError(f"plsa: wid has {N} entries, cnt {cnt.numel()}")
+        raise ValueError(f"{op}: wid has {N} entries, cnt {cnt.numel()}")
     if not _rises(doc_off, N):
-        raise ValueError("plsa: doc_off must have B + 1 entries rising from 0 to len(wid)")
+        raise ValueError(f"{op}: doc_off must have B + 1 entries rising from 0 to len(wid)")
     if N and (int(wid.min()) < 0 or int(wid.max()) >= V):
-        raise ValueError(f"plsa: word ids must be in 0..{V - 1}")
+        raise ValueError(f"{op}: word ids must be in 0..{V - 1}")
     return doc_off.numel() - 1
 
 
 def check_word_index(word_off: torch.Tensor, perm: torch.Tensor, uniq: torch.Tensor, V: int,
-                     wid: torch.Tensor | None = None) -> int:
+                     wid: torch.Tensor | None = None, op: str = "plsa") -> int:
     """Validate a batch's word index: ``uniq`` strictly ascending in ``0..V-1``, ``word_off``
     rising from 0 to ``N`` over ``U + 1`` entries, ``perm`` a permutation of ``0..N-1`` that
     ascends inside every word's run and, when the batch's ``wid`` is given, sorts it into
     ``uniq``'s runs.  Returns ``U``."""
-    _args.want("plsa", word_off, "word_off", torch.int32, 1)
-    _args.want("plsa", perm, "perm", torch.int32, 1)
-    _args.want("plsa", uniq, "uniq", torch.int32, 1)
-    _args.same_device("plsa", (word_off, perm, uniq), ("word_off", "perm", "uniq"))
+    _args.want(op, word_off, "word_off", torch.int32, 1)
+    _args.want(op, perm, "perm", torch.int32, 1)
+    _args.want(op, uniq, "uniq", torch.int32, 1)
+    _args.same_device(op, (word_off, perm, uniq), ("word_off", "perm", "uniq"))
     N, U = perm.numel(), uniq.numel()
     if word_off.numel() != U + 1 or not _rises(word_off, N):
-        raise ValueError("plsa: word_off must have len(uniq) + 1 entries rising from 0 to len(perm)")
+        raise ValueError(f"{op}: word_off must have len(uniq) + 1 entries rising from 0 to len(perm)")
     if U and (int(uniq[0]) < 0 or int(uniq[-1]) >= V or bool((uniq[1:] <= uniq[:-1]).any())):
-        raise ValueError(f"plsa: uniq must be strictly ascending word ids in 0..{V - 1}")
+        raise ValueError(f"{op}: uniq must be strictly ascending word ids in 0..{V - 1}")
     if N:
         if int(perm.min()) < 0 or int(perm.max()) >= N or \
                 not bool((torch.bincount(perm.long(), minlength=N) == 1).all()):
-            raise ValueError(f"plsa: perm must be a permutation of 0..{N - 1}")
+            raise ValueError(f"{op}: perm must be a permutation of 0..{N - 1}")
         if U == 0:
-            raise ValueError("plsa: perm has entries but uniq no word")
+            raise ValueError(f"{op}: perm has entries but uniq no word")
         run = torch.repeat_interleave(torch.arange(U, device=perm.device), (word_off[1:] - word_off[:-1]).long())
         if N > 1 and bool(((perm[1:] <= perm[:-1]) & (run[1:] == run[:-1])).any()):
-            raise ValueError("plsa: perm must ascend inside every word's run (sorted by (word, index))")
+            raise ValueError(f"{op}: perm must ascend inside every word's run (sorted by (word, index))")
         if wid is not None:
-            _args.want("plsa", wid, "wid", torch.int32, 1)
-            _args.same_device("plsa", (perm, wid), ("perm", "wid"))
+            _args.want(op, wid, "wid", torch.int32, 1)
+            _args.same_device(op, (perm, wid), ("perm", "wid"))
             if wid.numel() != N or not torch.equal(wid[perm.long()], uniq[run]):
-                raise ValueError("plsa: perm / word_off / uniq are not the sorted index of wid")
+                raise ValueError(f"{op}: perm / word_off / uniq are not the sorted index of wid")
     return U
 
 
-def batch_index(wid: torch.Tensor):
+def batch_index(wid: torch.Tensor, op: str = "plsa"):
     """``(perm, word_off, uniq)`` of a batch's word ids int32 [N]: a stable sort (non-zero
     indices by (word, index)) and its runs, on ``wid``'s device."""
-    _args.want("plsa", wid, "wid", torch.int32, 1)
+    _args.want(op, wid, "wid", torch.int32, 1)
     srt, perm = torch.sort(wid, stable=True)
     uniq, counts = torch.unique_consecutive(srt, return_counts=True)
     word_off = torch.zeros(uniq.numel() + 1, dtype=torch.int32, device=wid.device)
