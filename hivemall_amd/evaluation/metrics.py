@@ -18,6 +18,7 @@ import torch
 
 from ..registry import udaf
 from ..utils.options import Options, UDFArgumentException, opt
+from . import auc as _auc
 from . import ranking as _ranking
 
 
@@ -309,4 +310,16 @@ ndcg = udaf("ndcg")(_rank_udaf(ndcg_one))
 RANK_EVAL_CALLS = _ranking.RANK_EVAL_CALLS
 for _m, _fn in enumerate((precision_at, recall_at, hitrate, mrr, average_precision, ndcg)):
     _fn.grouped = _ranking.grouped_form(_m)
-auc.grouped = _ranking.grouped_form(6, array_form_only=True)
+_auc_array_grouped = _ranking.grouped_form(6, array_form_only=True)
+
+
+def _auc_grouped(arg_series, codes, n_groups, session=None):
+    """auc's two forms, told apart as auc itself does: by the first non-null score.  Arrays go to
+    the ranking-measures engine, scalars to the AUC engine (evaluation/auc.py)."""
+    if arg_series and isinstance(_first(arg_series[0]), (list, tuple, np.ndarray)):
+        return _auc_array_grouped(arg_series, codes, n_groups, session=session)
+    return _auc.scalar_grouped(arg_series, codes, n_groups, session=session)
+
+
+AUC_CALLS = _auc.AUC_CALLS
+auc.grouped = _auc_grouped
