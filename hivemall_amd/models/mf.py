@@ -327,10 +327,13 @@ class MatrixFactorization(_MFBase):
         self._step(u, i, torch.zeros(u.numel(), device=dev), train=False, pred=out)
         return out.cpu().numpy()
 
-    def recommend_topk(self, users=None, k: int = 10, exclude: tuple | None = None):
+    def recommend_topk(self, users=None, k: int = 10, exclude: tuple | None = None,
+                       precision: str = "bf16"):
         """Top-k items by mf_predict (mu + b_u + b_i + p_u.q_i) per user, best first:
         (scores [U,k], items [U,k]).  ``exclude`` = (row positions into ``users``, items).
         Fused MFMA score + top-k on the GPU (``ops/topk_mips.py``); k <= 64.
+        ``precision="fp32"`` scores the fp32 factor tables as they are, so the ranking is that
+        of the fp32 ``predict``; the default rounds them to bf16 first.
         (Predictions are not clipped to -min/-max here: clipping would only create ties.)"""
         st = self.state
         dev = st["P"].device
@@ -339,9 +342,10 @@ class MatrixFactorization(_MFBase):
         ex = None
         if exclude is not None:
             ex = topk_mips.exclusion_csr(exclude[0], exclude[1], uu.numel(), device=dev)
+        # fp32: mu + b_u is formed and added in fp64, so the returned score is rounded once
+        rb = (st["Bu"][uu].double() + st["mu"][0].double()) if precision == "fp32" else st["Bu"][uu] + st["mu"][0]
         ix, sc = topk_mips.mips_topk(st["P"][uu][:, : self.k], st["Q"][:, : self.k], k,
-                                     item_bias=st["Bi"], row_bias=st["Bu"][uu] + st["mu"][0],
-                                     exclude=ex)
+                                     item_bias=st["Bi"], row_bias=rb, exclude=ex, precision=precision)
         return sc, ix
 
     def model_table(self) -> pd.DataFrame:
@@ -615,12 +619,17 @@ class BPRMF(_MFBase):
         dt = torch.bfloat16 if U.is_cuda else torch.float32
         return (U.to(dt) @ st["Q"].to(dt).T).float() + st["Bi"][None, :]
 
-    def recommend_topk(self, users=None, k: int = 10, exclude: tuple | None = None):
+    def recommend_topk(self, users=None, k: int = 10, exclude: tuple | None = None,
+                       precision: str = "bf16"):
         """Top-k items per user, best first: (scores [U,k], items [U,k]).
 
         ``exclude`` = (row positions into ``users``, items) pairs to skip (already-seen items).
         On the GPU this is the fused MFMA score + top-k kernel (``ops/topk_mips.py``): the
-        user x item score matrix is never materialised.  k > 64 falls back to GEMM + topk."""
+        user x item score matrix is never materialised.  k > 64 falls back to GEMM + topk.
+        ``precision="fp32"`` scores the fp32 factor tables as they are (fused fp32 MFMA kernel,
+        fp32 GEMM in the fallback); the default rounds them to bf16 first."""
+        if precision not in topk_mips.PRECISIONS:
+            raise ValueError(f"recommend_topk: precision must be one of {topk_mips.PRECISIONS}")
         st = self.state
         U = st["P"] if users is None else st["P"][torch.as_tensor(users, device=st["P"].device).long()]
         if k <= topk_mips.KMAX:
@@ -628,9 +637,9 @@ class BPRMF(_MFBase):
             if exclude is not None:
                 ex = topk_mips.exclusion_csr(exclude[0], exclude[1], U.shape[0], device=U.device)
             ix, sc = topk_mips.mips_topk(U[:, : self.k], st["Q"][:, : self.k], k,
-                                         item_bias=st["Bi"], exclude=ex)
+                                         item_bias=st["Bi"], exclude=ex, precision=precision)
             return sc, ix
-        S = self.scores(users)
+        S = (U.float() @ st["Q"].float().T + st["Bi"][None, :]) if precision == "fp32" else self.scores(users)
         if exclude is not None:
             eu, ei = exclude
             S[torch.as_tensor(eu, device=S.device).long(), torch.as_tensor(ei, device=S.device).long()] = -float("inf")

@@ -10,6 +10,11 @@ running per-row top-k in LDS — the M x N score matrix never reaches HBM.  CPU 
 blocked fp32 ``matmul`` + ``topk`` with the same contract (and tie order: higher score first,
 then lower item index).
 
+``precision="bf16"`` (the default) rounds both operand tables to bf16 before the sweep: scores
+carry about 2^-9 relative error per product and the ranking is the ranking of those scores.
+``precision="fp32"`` runs the fp32 MFMA kernels of ``csrc/kernels/topk_mips_f32.hip`` on the
+tables as they are: fp32 products, fp32 accumulation, the ranking of the fp32 scores.
+
 This is the fused form of the reference's recommendation query
 ``each_top_k(k, user, mf_predict(...) / bprmf_predict(...), item)`` over the user x item
 join (core/src/main/java/hivemall/tools/EachTopKUDTF.java, mf/MFPredictionUDF.java,
@@ -26,15 +31,26 @@ from .. import _native
 
 _P = C.c_void_p
 _native.register_hip("hm_mips_topk", [C.c_int] * 7 + [_P] * 7 + [_P])
+_native.register_hip("hm_mips_topk_f32", [C.c_int] * 7 + [_P] * 7 + [_P])
 
 KMAX = 64
 _KD = (32, 64, 128, 256)
+_KD_F32 = (16, 32, 64, 128, 256)
+PRECISIONS = ("bf16", "fp32")
 
 
 def _pad_bf16(x: torch.Tensor, kd: int) -> torch.Tensor:
     out = torch.zeros(x.shape[0], kd, dtype=torch.bfloat16, device=x.device)
     out[:, : x.shape[1]] = x.to(torch.bfloat16)
     return out.contiguous()
+
+
+def _pad_f32(x: torch.Tensor, kd: int) -> torch.Tensor:
+    if x.shape[1] == kd and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        return x                                         # the kernel reads rows as 16-B chunks
+    out = torch.zeros(x.shape[0], kd, dtype=torch.float32, device=x.device)
+    out[:, : x.shape[1]] = x
+    return out
 
 
 def exclusion_csr(rows, items, n_rows: int, device=None):
@@ -73,9 +89,13 @@ def _merge(idx: torch.Tensor, sc: torch.Tensor, k: int):
 
 def mips_topk(Q: torch.Tensor, I: torch.Tensor, k: int, item_bias: torch.Tensor | None = None,
               row_bias: torch.Tensor | None = None, exclude: tuple | None = None,
-              exclude_self_offset: int | None = None, splits: int | None = None):
+              exclude_self_offset: int | None = None, splits: int | None = None,
+              precision: str = "bf16"):
     """Top-``k`` items per query row; returns (indices int64 [M,k], scores fp32 [M,k]).
     Missing entries (fewer than k admissible items) are index -1 / score -inf.
+
+    precision: operand type of the GPU kernel, ``"bf16"`` or ``"fp32"`` (CPU tensors always
+    run in fp32).
 
     exclude: (ptr int64 [M+1], items int32 sorted per row) from ``exclusion_csr``.
     exclude_self_offset: drop item ``q + offset`` for query ``q`` (0 for Q is I)."""
@@ -85,19 +105,27 @@ def mips_topk(Q: torch.Tensor, I: torch.Tensor, k: int, item_bias: torch.Tensor 
         raise ValueError(f"mips_topk: dimension mismatch {d} vs {d2}")
     if not 0 < k <= KMAX:
         raise ValueError(f"mips_topk: k must be in 1..{KMAX}")
+    if precision not in PRECISIONS:
+        raise ValueError(f"mips_topk: precision must be one of {PRECISIONS}, got {precision!r}")
     if Q.is_cuda:
-        return _mips_gpu(Q, I, k, item_bias, row_bias, exclude, exclude_self_offset, splits)
+        return _mips_gpu(Q, I, k, item_bias, row_bias, exclude, exclude_self_offset, splits, precision)
     return _mips_cpu(Q, I, k, item_bias, row_bias, exclude, exclude_self_offset)
 
 
-def _mips_gpu(Q, I, k, item_bias, row_bias, exclude, self_off, splits):
+def _mips_gpu(Q, I, k, item_bias, row_bias, exclude, self_off, splits, precision="bf16"):
     dev = Q.device
     M, d = Q.shape
     N = I.shape[0]
-    kd = next((x for x in _KD if x >= d), None)
+    kds = _KD_F32 if precision == "fp32" else _KD
+    kd = next((x for x in kds if x >= d), None)
     if kd is None:
-        raise ValueError(f"mips_topk: dimension {d} > {_KD[-1]}")
-    Qb, Ib = _pad_bf16(Q, kd), _pad_bf16(I.to(dev), kd)
+        raise ValueError(f"mips_topk: dimension {d} > {kds[-1]}")
+    if precision == "fp32":
+        entry = "hm_mips_topk_f32"
+        Qb, Ib = _pad_f32(Q, kd), _pad_f32(I.to(dev), kd)
+    else:
+        entry = "hm_mips_topk"
+        Qb, Ib = _pad_bf16(Q, kd), _pad_bf16(I.to(dev), kd)
     bias = item_bias.to(device=dev, dtype=torch.float32).contiguous() if item_bias is not None else None
     if splits is None:
         splits = _splits_for(M, N, torch.cuda.get_device_properties(dev).multi_processor_count)
@@ -109,16 +137,19 @@ def _mips_gpu(Q, I, k, item_bias, row_bias, exclude, self_off, splits):
     oi = torch.empty(splits, M, k, dtype=torch.int32, device=dev)
     os_ = torch.empty(splits, M, k, dtype=torch.float32, device=dev)
     p = _native.ptr
-    rc = _native.hip().hm_mips_topk(M, N, kd, k, splits, int(self_off is not None), int(self_off or 0),
-                                    p(Qb), p(Ib), p(bias), p(ex_ptr), p(ex_idx), p(oi), p(os_),
-                                    _native.stream_of(dev))
-    _native.check(rc, "hm_mips_topk")
+    rc = getattr(_native.hip(), entry)(M, N, kd, k, splits, int(self_off is not None), int(self_off or 0),
+                                       p(Qb), p(Ib), p(bias), p(ex_ptr), p(ex_idx), p(oi), p(os_),
+                                       _native.stream_of(dev))
+    _native.check(rc, entry)
     if splits > 1:
         idx, sc = _merge(oi, os_, k)
     else:
         idx, sc = oi[0], os_[0]
     idx = idx.long()
-    if row_bias is not None:
+    if row_bias is not None and row_bias.dtype == torch.float64:
+        # an fp64 row bias is added in fp64 and rounded once (the fp32 callers pass mu + b_u so)
+        sc = torch.where(idx >= 0, (sc.double() + row_bias.to(dev)[:, None]).float(), sc)
+    elif row_bias is not None:
         sc = torch.where(idx >= 0, sc + row_bias.to(dev, torch.float32)[:, None], sc)
     return idx, sc
 
