@@ -8,10 +8,12 @@ Prints one JSON line per variant: ms per full sweep, effective TFLOP/s of the sc
 and agreement of the fused result with the unfused one (fraction of identical top-k sets).
 Synthetic random-init factors (bf16 operands, fp32 accumulation in both variants).
 
-``--precision fp32`` builds fp32 operands and times three variants, alternating them over
+``--precision fp32`` builds fp32 operands and times four variants, alternating them over
 ``--repeats`` rounds in this one process: the fused fp32 MFMA kernel, a chunked fp32 ``matmul``
-+ ``torch.topk`` (the route the fp32 kernel replaces, and its yardstick) and the fused bf16
-kernel on the same tables.  Each line carries the median, the fastest and the slowest round."""
++ ``torch.topk`` (the route the fp32 kernel replaces, and its yardstick), the fused bf16
+kernel on the same tables and the chunked bf16 ``matmul`` + ``torch.topk``.  Each line carries
+the median, the fastest and the slowest round.  ``--k`` up to 256: above 64 the fused variants
+are the kernels of ``csrc/kernels/topk_mips_wide.hip``."""
 from __future__ import annotations
 
 import argparse
@@ -58,10 +60,21 @@ def main_fp32(a):
             outs_s.append(t.values)
         return torch.cat(outs_i), torch.cat(outs_s)
 
+    Ub, Vb = U.bfloat16(), V.bfloat16()
+
+    def unfused_bf16():                      # BPRMF.recommend_topk's route above topk_mips.KMAX
+        outs_i, outs_s = [], []
+        for r0 in range(0, a.users, a.chunk):
+            t = torch.topk((Ub[r0:r0 + a.chunk] @ Vb.T).float() + bias[None, :], a.k, dim=1)
+            outs_i.append(t.indices)
+            outs_s.append(t.values)
+        return torch.cat(outs_i), torch.cat(outs_s)
+
     variants = {
         "fused_fp32_mfma_topk": lambda: mips_topk(U, V, a.k, item_bias=bias, precision="fp32"),
         "gemm_fp32+torch.topk": unfused,
         "fused_bf16_mfma_topk": lambda: mips_topk(U, V, a.k, item_bias=bias, precision="bf16"),
+        "gemm_bf16+torch.topk": unfused_bf16,
     }
     ms = {n: [] for n in variants}
     out = {}
@@ -80,6 +93,8 @@ def main_fp32(a):
         if n == "gemm_fp32+torch.topk":
             rec.update(speedup_fused_fp32=round(med[n] / med["fused_fp32_mfma_topk"], 2),
                        same_topk_set_frac=round(same, 4), max_score_diff=(fs - us).abs().max().item())
+        if n == "gemm_bf16+torch.topk":
+            rec.update(speedup_fused_bf16=round(med[n] / med["fused_bf16_mfma_topk"], 2))
         print(json.dumps(rec), flush=True)
 
 

@@ -707,15 +707,16 @@ each_top_k.wants_session = True
 def topk_similar(X: torch.Tensor, Y: torch.Tensor | None = None, k: int = 10, precision: str = "bf16"):
     """Batched cosine top-k on the device: (scores, indices) of the k most similar rows of Y
     for every row of X (self-matches excluded when Y is None).  On the GPU ``precision="bf16"``
-    rounds the normalised rows to bf16 before the products; ``"fp32"`` keeps them in fp32."""
+    rounds the normalised rows to bf16 before the products; ``"fp32"`` keeps them in fp32.
+    The fused kernels hold k <= ``ops.topk_mips.KMAX`` (256) and up to 256 columns."""
     if precision not in ("bf16", "fp32"):
         raise ValueError(f"topk_similar: precision must be 'bf16' or 'fp32', got {precision!r}")
     Xn = torch.nn.functional.normalize(X.float(), dim=1)
     Yn = Xn if Y is None else torch.nn.functional.normalize(Y.float(), dim=1)
-    if k <= 64 and Xn.shape[1] <= 256:
-        # fused MFMA similarity + running top-k (ops/topk_mips.py): no N x N matrix in HBM
-        from ..ops.topk_mips import mips_topk
+    from ..ops.topk_mips import KMAX, mips_topk
 
+    if k <= KMAX and Xn.shape[1] <= 256:
+        # fused MFMA similarity + running top-k (ops/topk_mips.py): no N x N matrix in HBM
         ix, sc = mips_topk(Xn, Yn, min(k, Yn.shape[0]), exclude_self_offset=0 if Y is None else None,
                            precision=precision)
         return sc, ix

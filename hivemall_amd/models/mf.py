@@ -331,7 +331,7 @@ class MatrixFactorization(_MFBase):
                        precision: str = "bf16"):
         """Top-k items by mf_predict (mu + b_u + b_i + p_u.q_i) per user, best first:
         (scores [U,k], items [U,k]).  ``exclude`` = (row positions into ``users``, items).
-        Fused MFMA score + top-k on the GPU (``ops/topk_mips.py``); k <= 64.
+        Fused MFMA score + top-k on the GPU (``ops/topk_mips.py``); k <= 256.
         ``precision="fp32"`` scores the fp32 factor tables as they are, so the ranking is that
         of the fp32 ``predict``; the default rounds them to bf16 first.
         (Predictions are not clipped to -min/-max here: clipping would only create ties.)"""
@@ -625,14 +625,16 @@ class BPRMF(_MFBase):
 
         ``exclude`` = (row positions into ``users``, items) pairs to skip (already-seen items).
         On the GPU this is the fused MFMA score + top-k kernel (``ops/topk_mips.py``): the
-        user x item score matrix is never materialised.  k > 64 falls back to GEMM + topk.
+        user x item score matrix is never materialised.  k > 128 runs GEMM + topk.
         ``precision="fp32"`` scores the fp32 factor tables as they are (fused fp32 MFMA kernel,
         fp32 GEMM in the fallback); the default rounds them to bf16 first."""
         if precision not in topk_mips.PRECISIONS:
             raise ValueError(f"recommend_topk: precision must be one of {topk_mips.PRECISIONS}")
         st = self.state
         U = st["P"] if users is None else st["P"][torch.as_tensor(users, device=st["P"].device).long()]
-        if k <= topk_mips.KMAX:
+        # the fused kernels hold k <= topk_mips.KMAX, but above 128 GEMM + topk measured faster
+        # at ML-20M shape (docs/perf_notes.md, "Fused top-k, k = 65..256")
+        if k <= 128:
             ex = None
             if exclude is not None:
                 ex = topk_mips.exclusion_csr(exclude[0], exclude[1], U.shape[0], device=U.device)

@@ -1,4 +1,4 @@
-"""Fused top-k maximum inner product search (``csrc/kernels/topk_mips.hip``).
+"""Fused top-k maximum inner product search (``csrc/kernels/topk_mips.hip``; ``k`` up to 256).
 
 ``mips_topk(Q, I, k)`` returns, for every query row, the ``k`` items with the largest
 ``<Q[q], I[n]> + item_bias[n]`` (+ ``row_bias[q]`` on the returned scores), best first,
@@ -14,6 +14,10 @@ then lower item index).
 carry about 2^-9 relative error per product and the ranking is the ranking of those scores.
 ``precision="fp32"`` runs the fp32 MFMA kernels of ``csrc/kernels/topk_mips_f32.hip`` on the
 tables as they are: fp32 products, fp32 accumulation, the ranking of the fp32 scores.
+
+``k <= 64`` runs the kernels of those two files; ``k`` in 65..256 runs
+``csrc/kernels/topk_mips_wide.hip`` (the same score tiles, a per-row buffer of 64-bit keys in LDS
+compacted by a bitonic sort), for either precision and with the same contract.
 
 This is the fused form of the reference's recommendation query
 ``each_top_k(k, user, mf_predict(...) / bprmf_predict(...), item)`` over the user x item
@@ -32,8 +36,11 @@ from .. import _native
 _P = C.c_void_p
 _native.register_hip("hm_mips_topk", [C.c_int] * 7 + [_P] * 7 + [_P])
 _native.register_hip("hm_mips_topk_f32", [C.c_int] * 7 + [_P] * 7 + [_P])
+_native.register_hip("hm_mips_topk_wide", [C.c_int] * 7 + [_P] * 7 + [_P])
+_native.register_hip("hm_mips_topk_wide_f32", [C.c_int] * 7 + [_P] * 7 + [_P])
 
-KMAX = 64
+KMAX = 256
+_K_NARROW = 64              # up to here the register / 96-slot kernels; above, topk_mips_wide.hip
 _KD = (32, 64, 128, 256)
 _KD_F32 = (16, 32, 64, 128, 256)
 PRECISIONS = ("bf16", "fp32")
@@ -70,6 +77,16 @@ def _splits_for(M: int, N: int, sms: int) -> int:
     s = 1
     # at least ~4 blocks per CU, each split still sweeping >= 8 tiles of 64 items
     while blocks * s < 4 * sms and N // (64 * s * 2) >= 8:
+        s *= 2
+    return s
+
+
+def _splits_for_wide(M: int, N: int, k: int, sms: int) -> int:
+    """Splits of the wide kernels (k > 64): one block a CU (64 rows, 32 above k = 128), and a
+    split is worth merging only while it sweeps at least 4 k (and 512) items."""
+    blocks = (M + 63) // 64 if k <= 128 else (M + 31) // 32
+    s = 1
+    while blocks * s < 2 * sms and N // (s * 2) >= max(512, 4 * k):
         s *= 2
     return s
 
@@ -120,15 +137,17 @@ def _mips_gpu(Q, I, k, item_bias, row_bias, exclude, self_off, splits, precision
     kd = next((x for x in kds if x >= d), None)
     if kd is None:
         raise ValueError(f"mips_topk: dimension {d} > {kds[-1]}")
+    wide = k > _K_NARROW
     if precision == "fp32":
-        entry = "hm_mips_topk_f32"
+        entry = "hm_mips_topk_wide_f32" if wide else "hm_mips_topk_f32"
         Qb, Ib = _pad_f32(Q, kd), _pad_f32(I.to(dev), kd)
     else:
-        entry = "hm_mips_topk"
+        entry = "hm_mips_topk_wide" if wide else "hm_mips_topk"
         Qb, Ib = _pad_bf16(Q, kd), _pad_bf16(I.to(dev), kd)
     bias = item_bias.to(device=dev, dtype=torch.float32).contiguous() if item_bias is not None else None
     if splits is None:
-        splits = _splits_for(M, N, torch.cuda.get_device_properties(dev).multi_processor_count)
+        sms = torch.cuda.get_device_properties(dev).multi_processor_count
+        splits = _splits_for_wide(M, N, k, sms) if wide else _splits_for(M, N, sms)
     ex_ptr = ex_idx = None
     if exclude is not None:
         ex_ptr, ex_idx = (t.to(dev).contiguous() for t in exclude)
