@@ -13,7 +13,9 @@ itself: ``ops.knn_sparse``); ``SLIM.fit`` (the SQL surface) groups the rows as u
 hands them over.  ``torch`` is the batched torch descent over
 NumPy Gram matrices, ``slim_cd_batched``, the reference the native engine is tested against.
 Both are fp64 throughout and follow the update and coordinate order of upstream's residual
-loop.
+loop.  ``SLIM.recommend_topk`` serves the fitted model: ``ops.slim.slim_topk``, a fused sparse
+score + top-k kernel with one workgroup per user (``csrc/kernels/slim_topk.hip``) and its C++
+twin, or under ``-engine torch`` a sparse ``R @ W^T`` and ``torch.topk``.
 
 ``train_kpa`` is a per-example sequential learner with two engines (``-engine auto|native|python``).
 ``python`` is the per-row loop over dicts below, the definition.  ``native`` is ``ops.kpa``: a
@@ -138,11 +140,53 @@ def _padded_neighbours(nbr, n: int) -> np.ndarray:
     return out
 
 
+def _model_csr(i, nn, w, n_items: int):
+    """Model triples as ``(mptr int64 [n_items + 1], mnn int32, mw fp64)``, rows by target item,
+    neighbours ascending inside a row."""
+    i, nn = np.asarray(i, dtype=np.int64), np.asarray(nn, dtype=np.int64)
+    order = np.lexsort((nn, i))
+    mptr = np.zeros(n_items + 1, dtype=np.int64)
+    np.cumsum(np.bincount(i, minlength=n_items), out=mptr[1:])
+    return mptr, nn[order].astype(np.int32), np.ascontiguousarray(np.asarray(w, dtype=np.float64)[order])
+
+
+def _slim_topk_torch(rowptr, cols, vals, mptr, mnn, mw, k: int, exclude_seen: bool, block: int = 4096):
+    """The torch formulation of ``ops.slim.slim_topk``: per block of users a sparse ``R @ W^T`` for
+    the scores and the same product over the patterns for "has a term", then ``torch.topk``.
+    Sums in torch's order, and ``topk`` breaks ties as it likes: equal to rounding only."""
+    import torch
+
+    dev, n_items, n_users = rowptr.device, mptr.numel() - 1, rowptr.numel() - 1
+    tgt = torch.repeat_interleave(torch.arange(n_items, device=dev), mptr[1:] - mptr[:-1])
+    at = torch.stack([mnn.long(), tgt])                                   # W^T: [nn, i]
+    Wt = torch.sparse_coo_tensor(at, mw, (n_items, n_items)).coalesce()
+    Wt1 = torch.sparse_coo_tensor(at, torch.ones_like(mw), (n_items, n_items)).coalesce()
+    items = torch.full((n_users, k), -1, dtype=torch.int32, device=dev)
+    scores = torch.full((n_users, k), float("-inf"), dtype=torch.float64, device=dev)
+    kk = min(k, n_items)
+    for u0 in range(0, n_users if kk else 0, block):
+        u1 = min(u0 + block, n_users)
+        p0, p1 = int(rowptr[u0]), int(rowptr[u1])
+        row = torch.repeat_interleave(torch.arange(u1 - u0, device=dev), rowptr[u0 + 1:u1 + 1] - rowptr[u0:u1])
+        ix = torch.stack([row, cols[p0:p1].long()])
+        Rb = torch.sparse_coo_tensor(ix, vals[p0:p1], (u1 - u0, n_items))
+        Rb1 = torch.sparse_coo_tensor(ix, torch.ones_like(vals[p0:p1]), (u1 - u0, n_items))
+        s = torch.sparse.mm(Rb, Wt).to_dense()
+        s[torch.sparse.mm(Rb1, Wt1).to_dense() == 0] = float("-inf")
+        if exclude_seen:
+            s[ix[0], ix[1]] = float("-inf")
+        top, idx = torch.topk(s, kk, dim=1)
+        scores[u0:u1, :kk] = top
+        items[u0:u1, :kk] = torch.where(torch.isinf(top) & (top < 0), -1, idx).to(torch.int32)
+    return items, scores
+
+
 class SLIM(Learner):
     """For every item i: min_w ½||r_i − Σ_j w_j r_j||² + ½λ2||w||² + λ1||w||₁, w ≥ 0, over the
     item's kNN neighbours j (coordinate descent with soft thresholding)."""
     NAME = "train_slim"
     OPTIONS = SLIM_OPTS
+    _index = None           # (mptr, mnn, mw) by column number after fit_csc: model_index()
 
     def engine(self) -> str:
         """``-engine`` resolved: "native" (ops.slim: the gfx950 kernels on a cuda device, their
@@ -210,13 +254,16 @@ class SLIM(Learner):
             nbl.append([column(j, g["nb"][j]) for j in nbs])
         if not targets:
             self.table = pd.DataFrame([], columns=["i", "nn", "w"])
+            self._index = None
             return self
         if len(uix) > np.iinfo(np.int32).max:
             raise UDFArgumentException(f"{self.NAME}: more than 2^31 - 1 distinct users")
         colptr = np.zeros(len(labels) + 1, dtype=np.int64)
         np.cumsum(lens, out=colptr[1:])
         R = (colptr, np.concatenate(rws).astype(np.int32), np.concatenate(vls))
-        return self.fit_csc(R, targets, nbl, item_ids=labels)
+        self.fit_csc(R, targets, nbl, item_ids=labels)
+        self._index = None          # these columns are rating vectors, not the caller's items
+        return self
 
     def fit_csc(self, R, targets, nbr=None, item_ids=None, knn=None):
         """Columnar entry point: ``R`` holds the rating vectors as the columns of a
@@ -304,6 +351,7 @@ class SLIM(Learner):
         # .tolist(): Python scalars, so that pandas infers the id columns as it does from row tuples
         self.table = pd.DataFrame({"i": labels[targets[t]].tolist(), "nn": labels[nb[t, k]].tolist(),
                                    "w": W[t, k]}, columns=["i", "nn", "w"])
+        self._index = _model_csr(targets[t], nb[t, k], W[t, k], n_cols)
         return self
 
     def _fit_groups_torch(self, groups: dict):
@@ -336,10 +384,86 @@ class SLIM(Learner):
                     if W[n, k] != 0:
                         rows.append((i, j, float(W[n, k])))
         self.table = pd.DataFrame(rows, columns=["i", "nn", "w"])
+        self._index = None
         return self
 
     def model_table(self) -> pd.DataFrame:
         return self.table
+
+    def model_index(self, n_items: int | None = None):
+        """The model as a CSR over target items, ``(mptr int64 [I + 1], mnn int32, mw fp64)`` in
+        NumPy: what ``fit_csc`` kept (item = column number, ``I`` = the fit's column count whatever
+        ``n_items`` says), or, after ``fit``, built from the model table, whose ``i`` / ``nn`` labels
+        must then be non-negative integers (``I`` = the largest label + 1, or ``n_items`` if larger).
+        A model that holds an (item, neighbour) pair twice, as ``fit_csc`` produces for a repeated
+        entry of ``targets`` or a repeated neighbour, raises ``ValueError``."""
+        if self._index is not None:
+            return self._no_repeats(self._index)
+        try:
+            i = np.asarray(self.table["i"].tolist(), dtype=np.int64)
+            nn = np.asarray(self.table["nn"].tolist(), dtype=np.int64)
+        except (TypeError, ValueError, OverflowError) as ex:
+            raise ValueError(f"{self.NAME}: recommend_topk wants integer item ids in the model table: {ex}") from ex
+        if len(i) and min(i.min(), nn.min()) < 0:
+            raise ValueError(f"{self.NAME}: recommend_topk wants non-negative item ids in the model table")
+        top = int(max(i.max(), nn.max())) + 1 if len(i) else 0
+        return self._no_repeats(_model_csr(i, nn, self.table["w"].to_numpy(dtype=np.float64),
+                                           max(top, n_items or 0)))
+
+    def _no_repeats(self, index):
+        mptr, mnn, _ = index
+        row = np.repeat(np.arange(len(mptr) - 1), np.diff(mptr))
+        twice = np.flatnonzero((row[1:] == row[:-1]) & (mnn[1:] == mnn[:-1]))
+        if len(twice):
+            raise ValueError(f"{self.NAME}: the model holds neighbour {int(mnn[twice[0]])} of item "
+                             f"{int(row[twice[0]])} twice (a repeated target or neighbour in the fit)")
+        return index
+
+    def recommend_topk(self, R, users=None, k: int = 10, exclude_seen: bool = True):
+        """Top-k items per user by ``score(u, i) = sum_nn w[i, nn] * r[u, nn]``, best first:
+        ``(scores fp64 [U, k], items int32 [U, k])``, padded with ``-inf`` / ``-1`` where a user has
+        fewer than ``k`` candidates (``docs/compat.md``, SLIM recommendation).
+
+        ``R`` holds the ratings as a ``utils.matrix.CSRMatrix`` or a ``(rowptr, cols, vals)``
+        triple (row = user, columns in the numbering of ``fit_csc``'s ``item_ids``, and no column
+        beyond those the fit saw: ``ValueError``); ``users`` selects rows of it.  ``exclude_seen``
+        keeps a user's own items out.  Both engines check their arguments with
+        ``ops.slim.check_topk``.  ``-engine native``
+        runs ``ops.slim.slim_topk`` on the learner's device (the fused kernel of
+        ``csrc/kernels/slim_topk.hip``, its C++ twin on a CPU device); ``-engine torch`` is a
+        sparse ``R @ W^T`` and ``torch.topk`` in user blocks, equal to rounding only."""
+        import torch
+
+        from ..ops import slim as S
+        from ..utils.matrix import CSRMatrix
+
+        n_cols = None
+        if isinstance(R, CSRMatrix):
+            n_cols = R.n_cols
+            R = (R.indptr, R.indices, R.values)
+        try:
+            rowptr = np.ascontiguousarray(R[0], dtype=np.int64)
+            cols = np.ascontiguousarray(R[1], dtype=np.int32)
+            vals = np.ascontiguousarray(R[2], dtype=np.float64)
+        except (TypeError, ValueError) as ex:
+            raise ValueError(f"{self.NAME}: recommend_topk wants numeric (rowptr, cols, vals): {ex}") from ex
+        if users is not None:
+            uu = np.asarray(users, dtype=np.int64).reshape(-1)
+            if len(uu) and (uu.min() < 0 or uu.max() >= len(rowptr) - 1):
+                raise ValueError(f"{self.NAME}: users must be rows of R, 0..{len(rowptr) - 2}")
+            lens = rowptr[uu + 1] - rowptr[uu]
+            sub = np.zeros(len(uu) + 1, dtype=np.int64)
+            np.cumsum(lens, out=sub[1:])
+            take = np.repeat(rowptr[uu] - sub[:-1], lens) + np.arange(sub[-1])
+            rowptr, cols, vals = sub, cols[take], vals[take]
+        mptr, mnn, mw = self.model_index(max(n_cols or 0, int(cols.max()) + 1 if len(cols) else 0))
+        dev = self.device
+        tensors = [torch.from_numpy(a).to(dev) for a in (rowptr, cols, vals, mptr, mnn, mw)]
+        if self.engine() == "native":
+            items, scores = S.slim_topk(*tensors, k, exclude_seen=exclude_seen)
+        else:
+            items, scores = _slim_topk_torch(*tensors, S.check_topk(*tensors, k)[2], exclude_seen)
+        return scores, items
 
 
 KPA_OPTS = [
